@@ -1,23 +1,29 @@
 #!/usr/bin/env python
 """bench.py — images/sec of the Darknet-19 YOLOv2 hot path on MI355X (BASELINE.json metric: train + detect at 1/2/4/8 GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        # N > 1: re-launches itself as N ranks (one process per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     # N > 1: re-launches itself as N ranks (one process per GPU)
+
+A plain run sets up, warms up, times the K steps of the headline leg and prints the result line; --dump-outputs DIR then writes what the
+last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample of every larger array), on inputs that
+are a function of the arguments only, so that two builds can be compared output for output.  --full adds every other leg and figure below
+(the CPU baseline, the other workloads, per-kernel tables and rooflines, the contention rehearsal, the no-wrapper step at N > 1) and
+writes the long form to --tables.
 
 Launch.  With WORLD_SIZE unset and --gpus N > 1 the script re-executes itself under `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`; launched by the driver through torch.distributed.run it reads
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.  `ranks_seen` in the output is an RCCL all-reduce of ones.
 
-Legs (every timed region: W untimed warm-up steps, barrier + synchronize, EXACTLY K steps, barrier + synchronize, MAX over ranks):
+Legs (every timed region: W untimed warm-up steps - at least 5 for train - barrier + synchronize, EXACTLY K steps, barrier + synchronize, MAX over ranks):
   detect   BASELINE configs[1]: 416x416 batch-32 inference per GPU = conv stack + decode + visibility filter + NMS, inputs
            resident in HBM, K hipGraph replays rotating over 4 different resident batches.  N > 1: replicas only (no collective).
   train    BASELINE configs[2]: VOC-20 batch-64 per GPU: forward (batch-stat BN) + region loss + backward + fused SGD
            (lr 1e-3, momentum 0.9; quick_start.sh:71).  N > 1: data parallel through train.ensure_model (bucketed RCCL
-           all-reduce overlapped with backward, positive-count all-reduce), weak scaling; the same step WITHOUT the wrapper is
+           all-reduce overlapped with backward, positive-count all-reduce), weak scaling; with --full the same step WITHOUT the wrapper is
            timed beside it on every rank (`train.single_gpu_images_per_sec`: the denominator of the DP scaling efficiency).
   Headline `value`: the batch-64 training step (BASELINE configs[2]) at EVERY N - one workload for the whole scaling curve (north_star:
-           ">= 6x DP scaling 1 -> 8"); detect is reported beside it (`roofline.detect_*` / `summary.detect_*`).  --headline overrides.
+           ">= 6x DP scaling 1 -> 8"); with --full detect is reported beside it (`roofline.detect_*` / `summary.detect_*`).  --headline overrides.
 
-Roofline (N = 1, measured in this run with the library's per-kernel HIP-event hooks, y2_prof_*, on the launch stream):
+--full only.  Roofline (N = 1, measured in this run with the library's per-kernel HIP-event hooks, y2_prof_*, on the launch stream):
   roofline         dominant MFMA kernel TEMPLATE of the headline step: executed multiply-add FLOPs per step of all its launches / its time per step against
                    the fp32-input MFMA peak (157.3 TFLOP/s).  `frac`: time from the committed rocprofv3 trace of the timed schedule (profiles/*_traffic.json,
                    same kernel sources, same launches per step; else the event-hook figure, see `frac_source`); `frac_uncontended`: HIP event pairs per launch
@@ -90,6 +96,8 @@ def parse_args():
     ap.add_argument('--resnet-batch', type=int, default=32, help='per-GPU batch of the ResNet-50 leg')
     ap.add_argument('--tables', default='', help='where the long form of the result (per-kernel tables, plans) is written (default gpurun_out/bench_full.json)')
     ap.add_argument('--dry-run', action='store_true', help='no GPU: exercise launch / rendezvous / DP wrapper / timing protocol with a stand-in CPU workload (gloo); the numbers mean nothing')
+    ap.add_argument('--full', action='store_true', help='every leg and figure beside the headline (see the module docstring); without it only the headline leg runs')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
     return ap.parse_args()
 
 
@@ -177,11 +185,12 @@ class Ctx(object):
         return t.item()
 
     def timed(self, fn, steps):
-        """barrier + synchronize | EXACTLY `steps` calls | barrier + synchronize; MAX over ranks.  Returns (seconds, host seconds)."""
+        """barrier + synchronize | EXACTLY `steps` calls | barrier + synchronize; MAX over ranks.  Returns (seconds, host seconds);
+        `self.last` holds what the last call returned."""
         self.barrier()
         t0 = time.perf_counter()
         for i in range(steps):
-            fn(i)
+            self.last = fn(i)
         host = time.perf_counter() - t0
         self.barrier()
         return self.max_over_ranks(time.perf_counter() - t0), host
@@ -196,6 +205,65 @@ def release_memory():
     gc.collect()
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
+
+
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs: all files together
+
+
+def wants_outputs(args, ctx, leg):
+    """--dump-outputs is given and `leg` is the headline: rank 0 keeps what the leg's last timed step returned."""
+    return bool(args.dump_outputs) and ctx.rank == 0 and args.headline == leg
+
+
+def host_arrays(tensors, seed=0):
+    """{name: tensor} -> {name: numpy array}: floating point as float32 (float64 stays float64), everything else as float64.  An array of more
+    elements than its share of DUMP_BYTES (8 bytes each) is replaced by the same seeded sample of positions of its flattened form in every run."""
+    import numpy as np
+    import torch
+    cap = (DUMP_BYTES - 4096 * len(tensors)) // (8 * max(1, len(tensors)))
+    out = {}
+    for name, t in tensors.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(seed).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        out[name] = t.cpu().numpy()
+    return out
+
+
+def train_outputs(r, module):
+    """What a caller of train.iterate receives from one step: its return value (the predictions, the loss terms, their weighted total) and the
+    parameters' .grad it leaves, with the parameters the optimizer step made of them (all parameters, flattened in module order)."""
+    import torch
+    t = {'pred_' + k: v for k, v in r['pred'].items() if isinstance(v, torch.Tensor)}
+    t.update({'loss_' + k: v for k, v in r['loss'].items()})
+    t['loss_total'] = r['loss_total']
+    ps = list(module.parameters())
+    t['grad'] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in ps])
+    t['param'] = torch.cat([p.detach().reshape(-1) for p in ps])
+    return host_arrays(t)
+
+
+def detect_outputs(d):
+    """The result dict of one detect step (detect.detect_batch); the entries of the candidate and survivor lists past their counts are unspecified
+    and written as -1."""
+    import torch
+    t = {k: v for k, v in d.items() if isinstance(v, torch.Tensor)}
+    for key, count in (('index', 'count'), ('keep', 'keep_count')):
+        if key in t and count in t:
+            v = t[key]
+            valid = torch.arange(v.shape[-1], device=v.device) < t[count].view(-1, 1).to(v.device)
+            t[key] = torch.where(valid, v, torch.full_like(v, -1))
+    return host_arrays(t)
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def kernel_table(fn, steps):
@@ -410,10 +478,9 @@ def detect_leg(args, ctx):
         def replay(i):
             g = i % len(runs)
             if streams is None:
-                runs[g].run()
-            else:
-                with torch.cuda.stream(streams[g % nstreams]):
-                    runs[g].run()
+                return runs[g].run()
+            with torch.cuda.stream(streams[g % nstreams]):
+                return runs[g].run()
         fn = replay if runs is not None else eager
         measure.nstreams, measure.runs = nstreams, runs
         for i in range(2 * len(xs)):
@@ -421,15 +488,16 @@ def detect_leg(args, ctx):
         dt, host = ctx.timed(fn, steps)
         return dt, host, table, runs is not None
 
-    dt, host, table, graphed = measure(args.steps, args.warmup, ctx.world == 1)
+    dt, host, table, graphed = measure(args.steps, args.warmup, ctx.world == 1 and args.full)
+    outputs = detect_outputs(ctx.last) if wants_outputs(args, ctx, 'detect') else None
     pipelined = getattr(measure, 'nstreams', 1)
     serial_dt = None
-    if pipelined > 1 and ctx.world == 1:          # the same graphs strictly one after the other: the latency of a step, reported beside the throughput
+    if pipelined > 1 and ctx.world == 1 and args.full:          # the same graphs strictly one after the other: the latency of a step, reported beside the throughput
         serial_steps = min(args.steps, 24)
         serial_dt = measure(serial_steps, 0, False, want_streams=1)[0] / serial_steps
         measure.nstreams = pipelined
     d2h_dt = None
-    if ctx.world == 1 and getattr(measure, 'runs', None):
+    if ctx.world == 1 and getattr(measure, 'runs', None) and args.full:
         # the reference hands the survivors to the host (utils/postprocess.py:34-49 returns a Python list; detect.py:69-79 indexes with it): the same replays, each
         # followed by the per-class expansion (y2_expand_classes) and the copy of the batch's detections to host memory (one copy per result buffer, one synchronisation)
         runs, nd = measure.runs, min(args.steps, 24)
@@ -514,7 +582,9 @@ def detect_leg(args, ctx):
                     _hip.SPLIT = ''
                     dnn._cache = None
                     dnn._plan_cache = None
-    state = {k: v.detach().cpu() for k, v in dnn.state_dict().items()} if (ctx.world == 1 and args.cpu_sample > 0 and args.model == 'darknet') else None
+    if outputs is not None:
+        out['_outputs'] = outputs
+    state = {k: v.detach().cpu() for k, v in dnn.state_dict().items()} if (ctx.world == 1 and args.full and args.cpu_sample > 0 and args.model == 'darknet') else None
     del inf, dnn
     release_memory()
     return out, roof, state, anchors
@@ -654,7 +724,7 @@ def train_leg(args, ctx):
            'optimizer': 'utils.optim.SGD(lr=1e-3, momentum=0.9): fused multi-tensor HIP kernel, torch.optim.SGD semantics',
            'parallelism': 'dp%d: one process per GPU, bucketed RCCL all-reduce from inside backward + positive-count all-reduce' % ctx.world if ctx.world > 1 else 'single GPU'}
     single = None
-    if ctx.world > 1:
+    if ctx.world > 1 and args.full:
         # the same step without the wrapper, every rank at once: per-GPU rate with zero communication (DP efficiency denominator)
         step, last, keep = make(False)
         for i in range(3):
@@ -666,9 +736,11 @@ def train_leg(args, ctx):
         del step, last, keep
         release_memory()
     step, last, keep = make(True)
-    for i in range(5):          # untimed: autotune, allocator, and (N > 1) the wrapper's one-time adoption of rank 0's algorithm choices at its 4th call
+    for i in range(max(5, args.warmup)):          # untimed: autotune, allocator, and (N > 1) the wrapper's one-time adoption of rank 0's algorithm choices at its 4th call
         step(i)
     dt, host = ctx.timed(step, steps)
+    if wants_outputs(args, ctx, 'train'):
+        out['_outputs'] = train_outputs(last['r'], keep[0])
     if ctx.world > 1:
         out['autotune_choices_synced'] = getattr(keep[1], 'tune_synced', None)
         st = getattr(keep[1], 'overlap_stats', None)
@@ -679,8 +751,9 @@ def train_leg(args, ctx):
             out['dp_exposed_comm_note'] = 'median time the compute stream waits for the outstanding all-reduces after backward has finished (event pair around the waits)'
     out.update({'images_per_sec': round(B * steps * ctx.world / dt, 2), 'ms_per_step': round(dt / steps * 1e3, 3), 'host_ms_per_step': round(host / steps * 1e3, 3),
                 'loss_total': float(last['r']['loss_total'].detach())})
-    out['host_issue_ms_per_step'] = issue_time(ctx, step)
-    if ctx.world == 1:
+    if args.full:
+        out['host_issue_ms_per_step'] = issue_time(ctx, step)
+    if ctx.world == 1 and args.full:
         c = contended_step_ms(ctx, step)
         if c is not None:
             out.update(c)
@@ -694,7 +767,7 @@ def train_leg(args, ctx):
         out['dp_speedup_vs_single_gpu'] = round(out['images_per_sec'] / single, 3)
     if per_img is not None:
         out['direct_equiv_tflops_per_gpu'] = round(per_img * B * steps / dt / 1e12, 2)
-    if ctx.world == 1:
+    if ctx.world == 1 and args.full:
         # per-kernel durations are taken with the weight gradients on the MAIN stream: in the timed two-stream schedule they co-run with
         # the BatchNorm / transform passes of the next layers and the kernels inflate each other's durations (sum 60 ms in a 40 ms step)
         from model import train_graph
@@ -779,6 +852,7 @@ def multiscale_leg(args, ctx):
         first_miss[S] = len(_hip.TUNE_MISSES) - miss0          # problem shapes that had to be MEASURED at this visit (0 with a complete default table)
     schedule = [S for _ in range(max(1, args.ms_cycles)) for S in sizes for _ in range(maintain)]
     dt, host = ctx.timed(lambda i: step(schedule[i]), len(schedule))
+    outputs = train_outputs(last['r'], inf) if wants_outputs(args, ctx, 'multiscale') else None
     issue = {S: issue_time(ctx, lambda i, S=S: step(S), 4) for S in (sizes[0], sizes[-1])}
     images = B * len(schedule) * ctx.world
     # per-step table (synchronised after every step: NOT the throughput number)
@@ -814,6 +888,8 @@ def multiscale_leg(args, ctx):
         out['direct_equiv_tflops_per_gpu'] = round(per_img * B * len(schedule) / dt / 1e12, 2)
     if ctx.world > 1:
         out['autotune_choices_synced'] = getattr(m, 'tune_synced', None)
+    if outputs is not None:
+        out['_outputs'] = outputs
     del m, inf, opt, data
     torch.cuda.empty_cache()
     return out
@@ -1102,7 +1178,7 @@ def compact_line(head, roof, extra, cb, tables_at=None, limit=LINE_LIMIT):
                 r[k] = r[k][:157] + '...'
         r.update({k: v for k, v in extra.items() if not isinstance(v, (dict, list))})
         out['roofline'] = r
-    else:
+    elif extra:
         # N > 1: no per-kernel table is taken (the roofline and the CPU baseline are the N = 1 run's); the legs' scalars still belong in the line
         out['summary'] = {k: v for k, v in extra.items() if not isinstance(v, (dict, list))}
     if cb is not None:
@@ -1157,8 +1233,11 @@ def main():
     if args.no_train and headline == 'train':
         headline = 'detect'
     label = {'darknet': 'Darknet-19', 'tiny': 'tiny-yolo'}.get(args.model, args.model)
+    args.headline = 'multiscale' if args.multiscale else headline          # (the leg whose outputs --dump-outputs writes)
 
     if args.dry_run:
+        if args.dump_outputs:
+            raise SystemExit('bench.py: --dump-outputs writes what the GPU path computed; a dry run computes none of it')
         tr, de = dry_run(args, ctx)
         if ctx.rank == 0:
             src = tr if headline == 'train' else de
@@ -1181,7 +1260,7 @@ def main():
     # are capture + growth of the graph pool by ~15 GB per size; what a hipMalloc of that size costs depends on the BOX (10-12 ms at every size in four consecutive
     # processes on one, 0.5-0.9 s from 480-544 upwards on others - whatever this bench did before the leg: DESIGN.md 3.7).
     ms = None
-    if args.multiscale or (not args.no_multiscale and not args.no_train and args.model == 'darknet'):
+    if args.multiscale or (args.full and not args.no_multiscale and not args.no_train and args.model == 'darknet'):
         ctx.sync()
         time.sleep(args.settle)
         try:
@@ -1196,10 +1275,10 @@ def main():
     if ms is not None and ctx.gpu and not args.multiscale:
         ctx.sync()
         time.sleep(args.settle)          # (a leg measures lower right behind seconds of full load: DESIGN.md 5)
-    if not args.no_detect:
+    if not args.no_detect and (args.full or headline == 'detect'):
         det, roof, state, anchors = detect_leg(args, ctx)
     conv3 = None
-    if ctx.world == 1 and args.model == 'darknet' and not args.no_conv3:
+    if args.full and ctx.world == 1 and args.model == 'darknet' and not args.no_conv3:
         try:
             conv3 = conv3x3_leg(args, ctx)
         except Exception as e:
@@ -1207,9 +1286,10 @@ def main():
             traceback.print_exc()
             conv3 = {'error': '%s: %s' % (type(e).__name__, e)}
     tr = None
-    if not args.no_train:
-        ctx.sync()
-        time.sleep(args.settle)          # untimed pause between the inference legs and the training leg
+    if not args.no_train and (args.full or headline == 'train'):
+        if args.full:
+            ctx.sync()
+            time.sleep(args.settle)          # untimed pause between the inference legs and the training leg
         try:
             tr = train_leg(args, ctx)
         except Exception as e:
@@ -1219,14 +1299,14 @@ def main():
             traceback.print_exc()
             tr = {'error': '%s: %s' % (type(e).__name__, e)}
     lat = rn = None
-    if ctx.world == 1 and args.model == 'darknet' and not args.no_latency and not args.no_detect:
+    if args.full and ctx.world == 1 and args.model == 'darknet' and not args.no_latency and not args.no_detect:
         try:
             lat = latency_leg(args, ctx)
         except Exception as e:
             import traceback
             traceback.print_exc()
             lat = {'error': '%s: %s' % (type(e).__name__, e)}
-    if args.model == 'darknet' and not args.no_resnet and not args.no_train:
+    if args.full and args.model == 'darknet' and not args.no_resnet and not args.no_train:
         ctx.sync()
         try:
             rn = resnet_leg(args, ctx)
@@ -1235,6 +1315,9 @@ def main():
             traceback.print_exc()
             rn = {'error': '%s: %s' % (type(e).__name__, e)}
     if ctx.rank == 0:
+        outputs = [d.pop('_outputs') for d in (ms, det, tr) if isinstance(d, dict) and '_outputs' in d]
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs[0])
         metric, det_workload, tr_workload = naming(args, headline)
         if args.multiscale:
             value, msps, steps, workload = ms['images_per_sec'], ms['ms_per_step_mean'], ms['steps'], ms['workload']
@@ -1322,8 +1405,8 @@ def main():
             if v is not None:
                 full[k] = v
         full['scalars'] = extra
-        tables_at = write_tables(full, args.tables)
-        print(compact_line(head, roof, extra, cb, tables_at))
+        tables_at = write_tables(full, args.tables) if (args.full or args.tables) else None
+        print(compact_line(head, roof, extra if args.full else {}, cb, tables_at))
     if ctx.world > 1:
         ctx.dist.destroy_process_group()
 

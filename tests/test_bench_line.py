@@ -156,3 +156,30 @@ def test_trace_families_names_kernel_templates_like_the_hook_table(tmp_path):
     assert f['conv_fwd_dma_kernel'] == {'calls': 4, 'total_us': 1000.0} and f['loss_fwd_kernel']['calls'] == 2 and 'zero_fill_kernel' not in f
     import bench
     assert bench.family('conv_fwd_dma_kernel[grouped]') == 'conv_fwd_dma_kernel'
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: what one training step returns and the gradients / parameters it leaves, float32 / float64, at most 64 MB in all;
+    an array above its share is replaced by the same seeded sample in every run (two builds compare output for output)."""
+    import numpy as np
+    import torch
+    import bench
+    B = 64
+    r = {'pred': {'feature': torch.randn(B, 125, 13, 13), 'iou': torch.rand(B, 169, 5), 'logits': torch.randn(B, 169, 5, 20)},
+         'loss': {k: torch.rand(1) for k in ('foreground', 'background', 'center', 'size', 'cls')}, 'loss_total': torch.rand(1)}
+    m = torch.nn.Sequential(*[torch.nn.Linear(1024, 1024) for _ in range(24)])          # 25 M parameters
+    for p in m.parameters():
+        p.grad = torch.randn_like(p)
+    a, b = bench.train_outputs(r, m), bench.train_outputs(r, m)
+    assert set(a) == {'pred_feature', 'pred_iou', 'pred_logits', 'loss_foreground', 'loss_background', 'loss_center', 'loss_size', 'loss_cls', 'loss_total', 'grad', 'param'}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES
+    assert np.array_equal(a['pred_iou'], r['pred']['iou'].numpy().ravel()) and a['loss_total'][0] == r['loss_total'].item()
+    flat = torch.cat([p.grad.reshape(-1) for p in m.parameters()]).numpy()
+    assert a['grad'].size < flat.size and np.isin(a['grad'], flat).all()
+    bench.write_outputs(str(tmp_path / 'out'), a)
+    assert np.array_equal(np.load(str(tmp_path / 'out' / 'grad.npy')), a['grad'])
+    # detect: integer lists as float64, the entries past a list's count written as -1
+    d = bench.detect_outputs({'iou': torch.rand(2, 10), 'index': torch.arange(20).view(2, 10), 'count': torch.tensor([3, 0], dtype=torch.int32),
+                              'keep': torch.zeros(2, 4, dtype=torch.int32), 'keep_count': torch.tensor([1, 0], dtype=torch.int32)})
+    assert d['index'].dtype == np.float64 and d['index'].tolist() == [0, 1, 2] + [-1] * 17 and d['keep'].tolist() == [0] + [-1] * 7

@@ -306,7 +306,7 @@ def test_bench_two_ranks_share_the_one_gpu():
     import tempfile
     tables = os.path.join(tempfile.mkdtemp(), 'full.json')
     # (three small sizes for the multi-scale leg: two ranks' plans for ten sizes do not fit ONE GPU's memory - a property of this rig)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--train-steps', '3', '--cpu-sample', '0', '--no-resnet',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '4', '--warmup', '1', '--train-steps', '3', '--cpu-sample', '0', '--no-resnet',
                           '--ms-sizes', '320,352,384', '--ms-maintain', '4', '--tables', tables], capture_output=True, text=True, timeout=850, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]

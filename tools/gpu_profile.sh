@@ -7,7 +7,7 @@
 cd "$(dirname "$0")/.." || exit 1
 R=$PWD; O=$R/gpurun_out/prof; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
 [ "$Y2_PROFILE_EAGER" = "1" ] && export Y2_TRAIN_GRAPH=0
-DET="python $R/bench.py --headline detect --steps 8 --warmup 2 --cpu-sample 0 --no-train --no-direct-leg --no-conv3 --no-split-leg --no-multiscale --no-latency --no-resnet --tables $O/det_tables.json"
+DET="python $R/bench.py --full --headline detect --steps 8 --warmup 2 --cpu-sample 0 --no-train --no-direct-leg --no-conv3 --no-split-leg --no-multiscale --no-latency --no-resnet --tables $O/det_tables.json"
 TRN="python $R/tools/train_steady.py ${TRAIN_STEPS:-16} 6"
 export Y2_TUNE_CACHE=/tmp/y2_tune_r5.json
 $DET > /dev/null 2>&1; $TRN > $O/train_plain.json 2>/dev/null      # populate the algorithm cache: the profiled runs contain steady-state launches only
