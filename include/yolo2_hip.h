@@ -483,6 +483,29 @@ int y2_opt_adam(const y2_opt_tensor* tensors, int32_t count, float lr, float bet
 int y2_opt_grad_sumsq(const y2_opt_tensor* tensors, int32_t count, double* sumsq, y2_stream_t stream);
 int y2_opt_clip_grads(const y2_opt_tensor* tensors, int32_t count, const double* sumsq, float max_norm, y2_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution (model/mobilenet.py conv_dw: nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)), csrc/dwconv.hip.
+ * NHWC fp32, pad 1, stride 1 or 2, output Ho = (H-1)/stride + 1, Wo alike.  The filter w is read in its state_dict layout
+ * [C][1][3][3] (no packing).  16-B vector path when C and both pixel strides are multiples of 4 and the two activation bases are
+ * 16-B aligned; otherwise a scalar path (any width).  B*H*W < 2^31.  FLOPs = 2*9*B*Ho*Wo*C.
+ * ------------------------------------------------------------------------------------------------ */
+/* y[b,yo,xo,c] = LeakyReLU_slope(scale[c] * conv + shift[c]) from x [B,H,W] (pixel stride ldx) into y [B,Ho,Wo] (pixel stride ldy);
+ * scale / shift NULL = identity, slope 1 = no activation, 0 = ReLU.  stats: NULL, or [Y2_STATS_REPL][2*C] doubles (pre-zeroed)
+ * receiving the per-channel sum and sum of squares of the RAW convolution output (as y2_conv_params.stats); Y2_ENOSUP in
+ * deterministic mode (take them with y2_colstats_det). */
+int y2_dwconv_fwd(const float* x, const float* w, const float* scale, const float* shift, float slope, float* y, double* stats,
+                  int B, int H, int W, int C, int ldx, int ldy, int stride, y2_stream_t stream);
+/* Data gradient, gather form: dx [B,H,W,C] (pixel stride lddx; H, W = the forward's INPUT size) from dz [B,Ho,Wo,C] (pixel stride
+ * ldz).  Every element sums its contributing taps in a fixed order: no atomics, bit-reproducible. */
+int y2_dwconv_dgrad(const float* dz, const float* w, float* dx, int B, int H, int W, int C, int ldz, int lddx, int stride, y2_stream_t stream);
+/* Weight gradient dw [C][1][3][3] (state_dict layout, overwritten) from the forward input x [B,H,W,C] (pixel stride ldx) and dz
+ * [B,Ho,Wo,C] (pixel stride ldz).  Two fixed-order stages, no atomics: per-workgroup partial sums go to `workspace` (16-B aligned, at
+ * least y2_dwconv_wgrad_workspace_bytes(B, H, W, C, stride) bytes; else Y2_EALIGN / Y2_EINVAL), one reduce launch adds them.
+ * Bit-reproducible in both library modes. */
+int y2_dwconv_wgrad(const float* x, const float* dz, float* dw, float* workspace, long long workspace_bytes,
+                    int B, int H, int W, int C, int ldx, int ldz, int stride, y2_stream_t stream);
+long long y2_dwconv_wgrad_workspace_bytes(int B, int H, int W, int C, int stride);
+
 #ifdef __cplusplus
 }
 #endif

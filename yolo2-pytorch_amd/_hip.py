@@ -112,6 +112,10 @@ SIGNATURES = {
                             c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     'y2_maxpool_bwd': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     'y2_colsum': [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p],
+    'y2_dwconv_fwd': [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    'y2_dwconv_dgrad': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    'y2_dwconv_wgrad': [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    'y2_dwconv_wgrad_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
     'y2_f64_to_f32': [c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p],
     'y2_decode_bwd': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     'y2_region_loss_fwd': [c_void_p] * 11 + [c_int] * 6 + [c_float] + [c_void_p] * 5 + [c_void_p],
@@ -165,6 +169,7 @@ def lib():
         l.y2_conv_fwd_workspace_bytes.restype = ctypes.c_longlong
         l.y2_wino_wgrad_workspace_bytes.restype = ctypes.c_longlong
         l.y2_wino6_tiles.restype = ctypes.c_longlong
+        l.y2_dwconv_wgrad_workspace_bytes.restype = ctypes.c_longlong
         l.y2_wino_wgrad_workspace_bytes_ex.restype = ctypes.c_longlong
         l.y2_build_info.argtypes = []
         l.y2_build_info.restype = ctypes.c_char_p

@@ -1058,9 +1058,9 @@ def weighted_total(loss_, hparam):
 
 # ------------------------------------------------------------------------------------------------ ResNet plugins
 class _ROp(object):
-    """One recorded operation of the ResNet training forward (conv+BN+ReLU[+residual], or the stem max-pool)."""
+    """One recorded operation of the ResNet training forward (conv+BN+ReLU[+residual], the stem max-pool, or a depthwise conv+BN+ReLU)."""
     __slots__ = ('kind', 'conv', 'bn', 'x', 'ldx', 'h', 'w', 'ho', 'wo', 'stride', 'pad', 'k', 'cin', 'cout', 'z', 'scale', 'shift', 'mean', 'invstd',
-                 'residual', 'y', 'slope', 'first', 'pool')       # pool = (ksize, stride, pad, pad_end) of a 'pool' op
+                 'residual', 'y', 'slope', 'first', 'pool', 'filt')       # pool = (ksize, stride, pad, pad_end) of a 'pool' op; filt = the filter of a 'dw' op
 
 
 def resnet_forward(net, x, frozen=False):
@@ -1072,6 +1072,13 @@ def resnet_forward(net, x, frozen=False):
 
 def tiny_forward(net, x, frozen=False):
     """Training-mode forward of model.yolo2.Tiny (model/yolo2.py:140-173) through the same op-list graph as the ResNets."""
+    params = [p for p in net.parameters()]
+    out = ResNetTrainFn.apply(net, x, frozen, *params)
+    return out.permute(0, 3, 1, 2)
+
+
+def mobilenet_forward(net, x, frozen=False):
+    """Training-mode (or frozen-BN differentiable) forward of model.mobilenet.MobileNet through the same op-list graph as the ResNets."""
     params = [p for p in net.parameters()]
     out = ResNetTrainFn.apply(net, x, frozen, *params)
     return out.permute(0, 3, 1, 2)
@@ -1138,7 +1145,9 @@ class ResNetTrainFn(torch.autograd.Function):
     epilogue -> y2_bn_finalize (momentum 0.1) -> y2_bn_act_fwd_ex (affine [+ residual] + ReLU)}; backward in reverse with
     gradient fan-in per tensor: y2_bn_act_bwd_ex (ReLU mask from the recomputed pre-activation, BN backward, gradient of
     the residual input) -> y2_conv_wgrad_ex -> data gradient (stride 1: forward kernel on rotated weights; stride 2:
-    transposed mode of the general kernel); the stem max-pool goes through y2_maxpool_fwd / y2_maxpool_bwd."""
+    transposed mode of the general kernel); the stem max-pool goes through y2_maxpool_fwd / y2_maxpool_bwd.
+    Also the graph of model.yolo2.Tiny and of model.mobilenet.MobileNet, whose depthwise convolutions are 'dw' ops: y2_dwconv_fwd
+    (raw, BN statistics) -> y2_bn_finalize -> y2_bn_act_fwd_ex; backward y2_bn_act_bwd_ex -> y2_dwconv_wgrad -> y2_dwconv_dgrad."""
     MOMENTUM = 0.1
 
     @staticmethod
@@ -1197,6 +1206,9 @@ class ResNetTrainFn(torch.autograd.Function):
                 _hip.colstats_det(z, B * ho * wo, cout, cout, stats)
             op.kind, op.conv, op.bn, op.x, op.ldx, op.h, op.w, op.ho, op.wo = 'conv', conv, bn, xin, ldx, h, w, ho, wo
             op.stride, op.pad, op.k, op.cin, op.cout, op.z, op.residual, op.slope, op.first = stride, pad, k, cin_true, cout, z, residual, slope, first
+            return bn_act(op, conv, bn, stats, cout, ho, wo, slope, residual, momentum)
+
+        def bn_act(op, conv, bn, stats, cout, ho, wo, slope, residual, momentum):
             if bn is not None and frozen:
                 op.scale, op.shift = _new(dev, cout), _new(dev, cout)
                 _hip.check(L.y2_bn_fold(_hip.ptr(_hip.f32c(bn.weight.detach())), _hip.ptr(_hip.f32c(bn.bias.detach())), _hip.ptr(_hip.f32c(bn.running_mean)),
@@ -1213,11 +1225,32 @@ class ResNetTrainFn(torch.autograd.Function):
                 op.scale = op.mean = op.invstd = None
                 op.shift = _hip.f32c(conv.bias.detach()) if conv.bias is not None else None
             y = _new(dev, B, ho, wo, cout)
-            _hip.check(L.y2_bn_act_fwd_ex(_hip.ptr(z), _hip.ptr(op.scale), _hip.ptr(op.shift), slope, _hip.ptr(residual), cout if residual is not None else 0,
+            _hip.check(L.y2_bn_act_fwd_ex(_hip.ptr(op.z), _hip.ptr(op.scale), _hip.ptr(op.shift), slope, _hip.ptr(residual), cout if residual is not None else 0,
                                           _hip.ptr(y), None, B, ho, wo, cout, cout, cout, 0, 0, 0, 0, st), 'y2_bn_act_fwd_ex')
             op.y = y
             ops.append(op)
             return y, ho, wo, cout
+
+        def dwconv_bn(conv, bn, xin, C, h, w, stride):
+            # depthwise 3x3 / pad 1 (model/mobilenet.py conv_dw): raw output with the BN statistics, then the shared BN + ReLU step
+            op = _ROp()
+            weight = _hip.f32c(conv.weight.detach())
+            ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+            z = _new(dev, B, ho, wo, C)
+            stats = None
+            if not frozen:
+                stats = arena[used[0]:used[0] + _hip.STATS_REPL * 2 * C]
+                used[0] += _hip.STATS_REPL * 2 * C
+            det = _hip.ensure_deterministic(dev)
+            _hip.check(L.y2_dwconv_fwd(_hip.ptr(xin), _hip.ptr(weight), None, None, 1.0, _hip.ptr(z), None if (det or stats is None) else _hip.ptr(stats),
+                                       B, h, w, C, C, C, stride, st), 'y2_dwconv_fwd')
+            if det and stats is not None:
+                _hip.colstats_det(z, B * ho * wo, C, C, stats)
+            op.kind, op.conv, op.bn, op.x, op.ldx, op.h, op.w, op.ho, op.wo = 'dw', conv, bn, xin, C, h, w, ho, wo
+            op.stride, op.pad, op.k, op.cin, op.cout, op.z, op.residual, op.slope, op.first = stride, 1, 3, C, C, z, None, 0.0, False
+            op.filt = weight           # the data gradient reads the filter the forward read
+            y, ho, wo, _ = bn_act(op, conv, bn, stats, C, ho, wo, 0.0, None, None)
+            return y, ho, wo
 
         def maxpool(cur, h, w, ld, ksize, stride, pad, pad_end):
             pool = _ROp()
@@ -1247,6 +1280,22 @@ class ResNetTrainFn(torch.autograd.Function):
                 else:
                     cur, h, w = maxpool(cur, h, w, ld, 2, 2, 0, 0)
                 i += 1
+            ctx.net, ctx.ops, ctx.B = net, ops, B
+            ctx.param_ids = [id(p) for p in params]
+            return cur
+        from model import mobilenet as _mobilenet
+        if isinstance(net, _mobilenet.MobileNet):
+            # model/mobilenet.py:54-85: 3x3/s2 stem, 13 units of {depthwise 3x3 + BN + ReLU, pointwise 1x1 + BN + ReLU}, 1x1 head with bias
+            for name, conv in [('layers.0.conv', net.stem().conv)] + [('%s.pw.conv' % n, u.pw.conv) for n, u, _ in net.units()]:
+                if conv.weight.shape[0] % 4:
+                    raise RuntimeError('model.mobilenet: training needs widths that are multiples of 4 (%s.weight has %d output channels)'
+                                       % (name, conv.weight.shape[0]))
+            stem = net.stem()
+            cur, h, w, ld = conv_bn(stem.conv, stem.bn, x4, cpad, H, W, 2, 1, 0.0, first=True)
+            for _, unit, s in net.units():
+                cur, h, w = dwconv_bn(unit.dw.conv, unit.dw.bn, cur, ld, h, w, s)
+                cur, h, w, ld = conv_bn(unit.pw.conv, unit.pw.bn, cur, ld, h, w, 1, 0, 0.0)
+            cur, _, _, _ = conv_bn(net.head(), None, cur, ld, h, w, 1, 0, 1.0)
             ctx.net, ctx.ops, ctx.B = net, ops, B
             ctx.param_ids = [id(p) for p in params]
             return cur
@@ -1290,7 +1339,7 @@ class ResNetTrainFn(torch.autograd.Function):
         def dest(param):
             t = buffer_hook(param) if buffer_hook is not None else None
             return t if t is not None else _new(dev, *param.shape)
-        convs = [op for op in ops if op.kind == 'conv']
+        convs = [op for op in ops if op.kind in ('conv', 'dw')]
         # everything that must start from zero, filled by ONE launch: the fp64 sums of every BatchNorm backward, the accumulation targets of the
         # direct (split, atomically added) weight gradients, the zero-padded gradient of the 425-wide head
         sums_arena = torch.empty(2 * sum(op.cout for op in convs), dtype=torch.float64, device=dev)
@@ -1303,6 +1352,9 @@ class ResNetTrainFn(torch.autograd.Function):
             e = plan[id(op)] = dict(sums=sums_arena[off:off + 2 * cout], off=off)
             off += 2 * cout
             e['dz'] = None
+            if op.kind == 'dw':
+                e['wino'] = False
+                continue
             if cop != cout:
                 e['dz'] = _new(dev, B, op.ho, op.wo, cop)
                 zero.append(e['dz'])
@@ -1347,6 +1399,20 @@ class ResNetTrainFn(torch.autograd.Function):
                 affine.append((op.bn.weight, e['off'] + cout, cout))
             elif op.conv.bias is not None:
                 affine.append((op.conv.bias, e['off'], cout))
+            if op.kind == 'dw':
+                # ---- depthwise: weight gradient straight into the state_dict layout (two fixed-order stages), data gradient in gather form
+                C = op.cout
+                dw = dest(op.conv.weight)
+                nws = L.y2_dwconv_wgrad_workspace_bytes(B, op.h, op.w, C, op.stride)
+                ws = _new(dev, max(nws // 4, 4))
+                _hip.check(L.y2_dwconv_wgrad(_hip.ptr(op.x), _hip.ptr(dz), _hip.ptr(dw), _hip.ptr(ws), ws.numel() * 4, B, op.h, op.w, C, C, C, op.stride, st),
+                           'y2_dwconv_wgrad')
+                ready(op.conv.weight, dw)
+                op.z = None
+                dx = _new(dev, B, op.h, op.w, C)
+                _hip.check(L.y2_dwconv_dgrad(_hip.ptr(dz), _hip.ptr(op.filt), _hip.ptr(dx), B, op.h, op.w, C, C, C, op.stride, st), 'y2_dwconv_dgrad')
+                G.setdefault(id(op.x), []).append(dx)
+                continue
             # ---- weight gradient
             if e['wino']:
                 dwp = _hip.conv_wgrad(op.x, dz, B, op.h, op.w, cin, cin, cop, cop, k)     # direct or Winograd, by measurement
