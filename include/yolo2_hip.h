@@ -506,6 +506,39 @@ int y2_dwconv_wgrad(const float* x, const float* dz, float* dw, float* workspace
                     int B, int H, int W, int C, int ldx, int ldz, int stride, y2_stream_t stream);
 long long y2_dwconv_wgrad_workspace_bytes(int B, int H, int W, int C, int stride);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pre-activation kernels of the DenseNet plugin (model/densenet.py; torchvision's _DenseLayer / _Transition: BatchNorm -> ReLU -> 1x1
+ * convolution [-> AvgPool2d(2, 2)]), csrc/dense.hip.  NHWC fp32.  The input is a channel slice of a block buffer: x points at the slice's
+ * first channel, ldx is the buffer's pixel stride.  pre_scale / pre_shift [K] are the per-INPUT-channel affine (NULL = identity: 1 / 0),
+ * pre_slope the LeakyReLU slope behind it (0 = ReLU, 1 = none).  pool = 1: 2x2 / stride-2 average of the pre-activated input (H, W even),
+ * everything downstream at [B, H/2, W/2].  16-B vector path when the channel count and the pixel strides of the operands read are multiples
+ * of 4 and their bases 16-B aligned; otherwise a scalar path (any width).  B*H*W < 2^31.
+ * ------------------------------------------------------------------------------------------------ */
+/* out[m][coff + n] = LeakyReLU_slope(scale[n] * sum_k act_pre(pre_scale[k] * x[m][k] + pre_shift[k]) * w[n][k] + shift[n]) for the M = B*Ho*Wo
+ * output pixels: the pre-activation runs in the operand loader of an fp32-MFMA GEMM, nothing but the result goes to memory.
+ * w: [N][K], a 1x1 weight in its state_dict layout (no packing).  scale / shift [N] or NULL, slope, ldy / coff: as y2_conv_params.
+ * stats: NULL, or [Y2_STATS_REPL][2*N] doubles (pre-zeroed) receiving the sum and the sum of squares of the RAW products per output channel;
+ * Y2_ENOSUP in deterministic mode (take them with y2_colstats_det).  pool = 1: the window mean is formed in the loader and the GEMM
+ * runs at half resolution (average pooling and a 1x1 convolution commute).  FLOPs = 2*M*N*K. */
+int y2_preact_conv1x1_fwd(const float* x, const float* w, const float* pre_scale, const float* pre_shift, float pre_slope,
+                          const float* scale, const float* shift, float slope, float* y, double* stats,
+                          int B, int H, int W, int K, int ldx, int N, int ldy, int coff, int pool, y2_stream_t stream);
+/* The materialising form: out[m][c] = act_pre(pre_scale[c] * x[m][c] + pre_shift[c]) (pool = 1: its 2x2 window mean, summed in the order
+ * the GEMM loader uses) into out [B,Ho,Wo] with pixel stride ldo: the operand of the 1x1 weight gradient (y2_conv_wgrad, ksize 1). */
+int y2_preact_fwd(const float* x, const float* pre_scale, const float* pre_shift, float pre_slope, float* out,
+                  int B, int H, int W, int C, int ldx, int ldo, int pool, y2_stream_t stream);
+/* Backward of (BatchNorm with batch statistics | frozen BatchNorm | nothing) -> LeakyReLU [-> AvgPool 2x2] on a channel slice: has_bn = 1 / 2 / 0
+ * as y2_bn_act_bwd.  pre_scale / pre_shift: the forward's affine (rebuilds the activation mask; zero gradient at 0 like torch); mean, invstd,
+ * gamma [C] (has_bn != 0).  dA: gradient of the forward's output, [B,Ho,Wo] with pixel stride ldda (pool = 1: every element of a window
+ * receives dA / 4).  With g = the gradient behind the mask and xhat = (x - mean) * invstd:
+ *   sums [2C] fp64 = [sum g | sum g * xhat] = [d beta | d gamma] - pre-zeroed by the caller (fp64 atomics); in deterministic mode written
+ *   through a fixed tree of per-workgroup partial sums;
+ *   dx = gamma * invstd * (g - sum g / M - xhat * sum g xhat / M), M = B*H*W (has_bn 1);  g * gamma * invstd (has_bn 2);  g (has_bn 0),
+ * WRITTEN (accumulate = 0) or ADDED (accumulate = 1) to dx [B,H,W] with pixel stride lddx - the slice of the block's gradient buffer. */
+int y2_preact_bwd(const float* x, const float* pre_scale, const float* pre_shift, float pre_slope, const float* mean, const float* invstd,
+                  const float* gamma, const float* dA, int ldda, double* sums, float* dx, int lddx, int accumulate,
+                  int B, int H, int W, int C, int ldx, int pool, int has_bn, y2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,9 @@
 """Measure the per-layer algorithm choices for the BASELINE shapes on this MI355X and write them as the committed default table
 (yolo2-pytorch_amd/tune/default_gfx950.json, keyed by the hash of the kernel sources): detect at batch 1 / 8 / 32 and training at batch 64,
 Darknet-19 with 20 and 80 classes at every size of the multi-scale schedule (config.ini:39-40), plus ResNet-50 at 608x608 / 80 classes and
-the MobileNet plugin (model.mobilenet) at 416x416 / 20 classes: detect at batch 32, training at batch 64.
+the MobileNet plugin (model.mobilenet) at 416x416 / 20 classes: detect at batch 32, training at batch 64, plus DenseNet-121 (model.densenet) at
+416x416 / 20 classes: detect at batch 32 (its 3x3 layers with 32 output channels, and per pre-activated 1x1 shape the choice between the fused
+kernel and the two-kernel form).
 A fresh process then starts warm: `first_visit_ms` of the multi-scale leg drops from seconds to the cost of one untimed step."""
 import argparse
 import os
@@ -21,6 +23,7 @@ def main():
     ap.add_argument('--classes', default='20,80')
     ap.add_argument('--no-resnet', action='store_true')
     ap.add_argument('--no-mobilenet', action='store_true')
+    ap.add_argument('--no-densenet', action='store_true')
     args = ap.parse_args()
     os.environ['Y2_TUNE_DEFAULTS'] = '0'          # measure everything afresh
     import torch
@@ -80,6 +83,13 @@ def main():
         inf, anchors = mobilenet_bench.build(dev, 20)
         detect_shapes(inf, anchors, [(32, 416)])
         train_shapes(inf, anchors, 20, [(64, 416)])
+        del inf
+        torch.cuda.empty_cache()
+    if not args.no_densenet:
+        sys.path.insert(0, os.path.join(ROOT, 'tools'))
+        import densenet_bench
+        inf, anchors = densenet_bench.build(dev, 20)
+        detect_shapes(inf, anchors, [(32, 416)])
         del inf
         torch.cuda.empty_cache()
     n = _hip.save_tune_defaults(note='tools/make_tune_table.py on %s, torch %s' % (torch.cuda.get_device_name(0), torch.__version__))

@@ -116,6 +116,9 @@ SIGNATURES = {
     'y2_dwconv_dgrad': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     'y2_dwconv_wgrad': [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     'y2_dwconv_wgrad_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],
+    'y2_preact_conv1x1_fwd': [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p],
+    'y2_preact_fwd': [c_void_p, c_void_p, c_void_p, c_float, c_void_p] + [c_int] * 7 + [c_void_p],
+    'y2_preact_bwd': [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_int] * 7 + [c_void_p],
     'y2_f64_to_f32': [c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p],
     'y2_decode_bwd': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     'y2_region_loss_fwd': [c_void_p] * 11 + [c_int] * 6 + [c_float] + [c_void_p] * 5 + [c_void_p],
@@ -704,6 +707,21 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
     _TUNE[key] = list(best)
     _tune_save()
     return best
+
+
+def tune_lookup(key, dev):
+    """A choice other code keeps in the table next to the convolution algorithms (model.densenet: fused or two-kernel form per 1x1 shape); None when
+    the table has none."""
+    if str(dev) not in _DEFAULTS_SEEN:
+        load_tune_defaults(dev)
+    return _TUNE.get(key)
+
+
+def tune_store(key, value):
+    """Record a choice measured in this process (counted in TUNE_MISSES, persisted with Y2_TUNE_CACHE)."""
+    TUNE_MISSES.append(key)
+    _TUNE[key] = value
+    _tune_save()
 
 
 def export_tune():

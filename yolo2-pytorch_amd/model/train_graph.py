@@ -1084,6 +1084,273 @@ def mobilenet_forward(net, x, frozen=False):
     return out.permute(0, 3, 1, 2)
 
 
+def densenet_forward(net, x, frozen=False):
+    """Training-mode (or frozen-BN differentiable) forward of model.densenet.DenseNet through the op-list graph of the ResNets ('pre' / 'grow' ops)."""
+    params = [p for p in net.parameters()]
+    out = ResNetTrainFn.apply(net, x, frozen, *params)
+    return out.permute(0, 3, 1, 2)
+
+
+class _DOp(object):
+    """One recorded DenseNet operation.  kind 'pre': BatchNorm -> ReLU -> 1x1 convolution [-> AvgPool 2x2] on the first K channels of a block buffer
+    (norm1 + conv1 of a dense layer with its norm2 + ReLU behind it; a transition; norm5 + the head); kind 'grow': the raw 3x3 convolution that
+    appends growth_rate channels to the block buffer."""
+    __slots__ = ('kind', 'bn', 'conv', 'buf', 'gbuf', 'K', 'ld', 'h', 'w', 'pool', 'pre_slope', 'scale', 'shift', 'mean', 'invstd', 'N', 'z', 'bn2', 'scale2',
+                 'shift2', 'mean2', 'invstd2', 'a2', 'out', 'out_ld', 'out_off', 'role')
+
+
+def _dense_conv3(L, st, x, wp, y, B, H, W, cin, cout, ldy, coff, stats):
+    """The raw 3x3 / pad 1 convolution of a dense layer writing its cout channels at channel offset coff of a block buffer."""
+    p = _hip.ConvParams()
+    p.x, p.w, p.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
+    p.stats = stats.data_ptr() if stats is not None else None
+    p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, H, W, cin, cin, cout, 3
+    p.ldy, p.coff, p.slope, p.tile = ldy, coff, 1.0, 0
+    p.stride, p.pad_plus1 = 1, 2
+    u = _hip.wino_weight(wp, cout, cin) if _hip.wino_eligible(cout, cin, 3) else None
+    _hip.autotune_conv(p, x.device, wino_w=u)
+    _hip.conv_workspace(p, x.device)
+    _hip.check(L.y2_conv_fwd(ctypes.byref(p), st), 'y2_conv_fwd')
+
+
+def _densenet_fwd(ctx, net, L, st, dev, B, H, W, x4, cpad, frozen, take_stats, prepared, conv_bn, maxpool):
+    """model/densenet.py:29-65.  A dense block is one buffer [B, h, w, C_end]; the batch statistics of a slab of it (the stem's pooled output, a
+    transition's output, the growth_rate channels of a layer) are taken ONCE, by its producer, and every consumer's BatchNorm finalises from them
+    with its own gamma / beta and updates its own running statistics (the reference recomputes the identical statistics per consumer)."""
+    import torch.nn as nn
+    f = net.features
+    for name, m in net.named_modules():
+        if isinstance(m, nn.Conv2d) and m is not f.conv and (m.weight.shape[0] % 4 or (m.weight.shape[1] % 4 and m is not f.conv0)):
+            raise RuntimeError('model.densenet: training needs widths that are multiples of 4 (%s.weight is %s)' % (name, tuple(m.weight.shape)))
+    det = _hip.ensure_deterministic(dev)
+    MOM = ResNetTrainFn.MOMENTUM
+    dops = []
+
+    def slab_stats(view, M, C, ld):
+        """deterministic mode (and the stem's pooled slab): column statistics of a finished slab"""
+        stats = take_stats(C)
+        _hip.colstats_det(view, M, C, ld, stats)
+        return stats
+
+    def finalize(bn, slabs, C, count):
+        scale, shift = _new(dev, C), _new(dev, C)
+        gamma, beta = _hip.f32c(bn.weight.detach()), _hip.f32c(bn.bias.detach())
+        if frozen:
+            _hip.check(L.y2_bn_fold(_hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(_hip.f32c(bn.running_mean)), _hip.ptr(_hip.f32c(bn.running_var)), BN_EPS,
+                                    _hip.ptr(scale), _hip.ptr(shift), C, st), 'y2_bn_fold')
+            return scale, shift, _hip.f32c(bn.running_mean), torch.rsqrt(_hip.f32c(bn.running_var) + BN_EPS)
+        mean, invstd = _new(dev, C), _new(dev, C)
+        counter = _counter(bn)
+        covered = 0
+        for off, n, stats in slabs:
+            if off >= C:
+                break
+            assert off == covered and off + n <= C
+            _hip.check(L.y2_bn_finalize(_hip.ptr(stats), float(count), _hip.ptr(gamma[off:off + n]), _hip.ptr(beta[off:off + n]),
+                                        _hip.ptr(bn.running_mean[off:off + n]), _hip.ptr(bn.running_var[off:off + n]), MOM, BN_EPS,
+                                        _hip.ptr(scale[off:off + n]), _hip.ptr(shift[off:off + n]), _hip.ptr(mean[off:off + n]), _hip.ptr(invstd[off:off + n]), n,
+                                        _hip.ptr(counter) if off == 0 else None, st), 'y2_bn_finalize')
+            covered = off + n
+        assert covered == C
+        _hip.wrote([t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None])
+        return scale, shift, mean, invstd
+
+    def pre(role, bn, conv, buf, slabs, K, ld, h, w, pool, pre_slope, out, out_ld, out_off, shift=None, want_stats=False):
+        op = _DOp()
+        op.kind, op.role, op.bn, op.conv, op.buf, op.K, op.ld, op.h, op.w, op.pool, op.pre_slope = 'pre', role, bn, conv, buf, K, ld, h, w, pool, pre_slope
+        op.scale, op.shift, op.mean, op.invstd = finalize(bn, slabs, K, B * h * w)
+        op.N = N = conv.weight.shape[0]
+        op.out, op.out_ld, op.out_off, op.bn2 = out, out_ld, out_off, None
+        stats = take_stats(N) if (want_stats and not frozen) else None
+        _hip.check(L.y2_preact_conv1x1_fwd(_hip.ptr(buf), _hip.ptr(_hip.f32c(conv.weight.detach())), _hip.ptr(op.scale), _hip.ptr(op.shift), pre_slope, None,
+                                           _hip.ptr(shift), 1.0, _hip.ptr(out), None if det else _hip.ptr(stats), B, h, w, K, ld, N, out_ld, out_off, pool, st),
+                   'y2_preact_conv1x1_fwd')
+        ho, wo = (h // 2, w // 2) if pool else (h, w)
+        if det and stats is not None:
+            _hip.colstats_det(out.view(-1)[out_off:], B * ho * wo, N, out_ld, stats)
+        dops.append(op)
+        return op, stats
+
+    # ---- stem: conv0 + norm0 + ReLU + MaxPool2d(3, 2, 1) (the ResNet stem ops), copied into block buffer 1
+    c0 = f.conv0.weight.shape[0]
+    cur, h, w, _ = conv_bn(f.conv0, f.norm0, x4, cpad, H, W, 2, 3, 0.0, first=True)
+    pooled, h, w = maxpool(cur, h, w, c0, 3, 2, 1, 1)
+    c, buf, prev = c0, None, None
+    blocks = net.blocks()
+    for bi, (block, trans) in enumerate(blocks):
+        c_end = c + sum(layer.conv2.weight.shape[0] for layer in block)
+        nxt = _new(dev, B, h, w, c_end)
+        if bi == 0:
+            _hip.check(L.y2_bn_act_fwd(_hip.ptr(pooled), None, None, 1.0, _hip.ptr(nxt), None, B, h, w, c0, c0, c_end, 0, 0, 0, 0, st), 'y2_bn_act_fwd')
+            slabs = [(0, c0, None if frozen else slab_stats(pooled, B * h * w, c0, c0))]
+        else:
+            pbuf, pslabs, pc, ph, pw, ptr_ = prev
+            op, stats = pre('trans', ptr_.norm, ptr_.conv, pbuf, pslabs, pc, pc, ph, pw, 1, 0.0, nxt, c_end, 0, want_stats=True)
+            slabs = [(0, c, stats)]
+        buf = nxt
+        for layer in block:
+            n1, g = layer.conv1.weight.shape[0], layer.conv2.weight.shape[0]
+            z1 = _new(dev, B, h, w, n1)
+            op, stats1 = pre('layer', layer.norm1, layer.conv1, buf, slabs, c, c_end, h, w, 0, 0.0, z1, n1, 0, want_stats=True)
+            op.z, op.bn2 = z1, layer.norm2
+            op.scale2, op.shift2, op.mean2, op.invstd2 = finalize(layer.norm2, [(0, n1, stats1)], n1, B * h * w)
+            a2 = _new(dev, B, h, w, n1)
+            _hip.check(L.y2_bn_act_fwd_ex(_hip.ptr(z1), _hip.ptr(op.scale2), _hip.ptr(op.shift2), 0.0, None, 0, _hip.ptr(a2), None, B, h, w, n1, n1, n1, 0, 0, 0, 0, st),
+                       'y2_bn_act_fwd_ex')
+            op.a2 = a2
+            wp = prepared[layer.conv2]['wp']
+            gstats = take_stats(g) if not frozen else None
+            _dense_conv3(L, st, a2, wp, buf, B, h, w, n1, g, c_end, c, None if det else gstats)
+            if det and gstats is not None:
+                _hip.colstats_det(buf.view(-1)[c:], B * h * w, g, c_end, gstats)
+            grow = _DOp()
+            grow.kind, grow.conv, grow.buf, grow.K, grow.ld, grow.h, grow.w, grow.N, grow.a2, grow.out_off = 'grow', layer.conv2, buf, n1, c_end, h, w, g, a2, c
+            dops.append(grow)
+            slabs.append((c, g, gstats))
+            c += g
+        if trans is not None:
+            prev = (buf, slabs, c_end, h, w, trans)
+            c = trans.conv.weight.shape[0]
+            h, w = h // 2, w // 2
+    nout = f.conv.weight.shape[0]
+    out = _new(dev, B, h, w, nout)
+    op, _ = pre('head', f.norm5, f.conv, buf, slabs, c, c, h, w, 0, 1.0, out, nout, 0, shift=_hip.f32c(f.conv.bias.detach()))
+    op.z = out
+    ctx.dense = dict(ops=dops, pooled=pooled, c0=c0)
+    return out
+
+
+def _densenet_bwd(ctx, dout, ready, dest, buffer_hook):
+    """Reverse walk of the 'pre' / 'grow' ops.  Every block has ONE gradient buffer [B, h, w, C_end]: the block's consumer (transition / head) writes
+    all of it through y2_preact_bwd, every layer then reads the finished gradient of its own slab and ADDS its input gradient into the first K
+    channels.  Returns the gradient of the stem's pooled output (the ResNet stem ops finish the walk)."""
+    L, st = _hip.lib(), _hip.stream()
+    dense, B, net = ctx.dense, ctx.B, ctx.net
+    dev = dout.device
+    prepared = ctx.prepared
+    dops = dense['ops']
+    pres = [op for op in dops if op.kind == 'pre']
+    total = sum(2 * op.K + (2 * op.N if op.bn2 is not None else 0) for op in pres)
+    nout = pres[-1].N
+    sums_arena = torch.empty(total + 2 * nout, dtype=torch.float64, device=dev)
+    head = pres[-1]
+    head_cop = (nout + 3) // 4 * 4
+    head_dz = _new(dev, B, head.h, head.w, head_cop)
+    head_dwp, head_w = _new(dev, head_cop * head.K), _new(dev, head_cop, head.K, 1, 1)
+    zero = [sums_arena, head_dz, head_dwp, head_w]
+    wbuf = {}
+    for op in pres:          # the 1x1 weight gradients: [N][1][K] IS the state_dict layout; the direct kernel adds split partial sums into a zeroed buffer
+        if op.role != 'head':
+            wbuf[id(op)] = dest(op.conv.weight)
+            zero.append(wbuf[id(op)].view(-1))
+    for i in range(0, len(zero), 64):          # (Y2_MULTI_MAX_ITEMS entries per launch)
+        _hip.multi([(_hip.MULTI_ZERO, t, None) for t in zero[i:i + 64]], st)
+    has_bn = 2 if ctx.frozen else 1
+    affine, off = [], 0
+    gbufs = {}
+
+    def gbuf_of(op):
+        t = gbufs.get(id(op.buf))
+        if t is None:
+            t = gbufs[id(op.buf)] = _new(dev, *op.buf.shape)
+        return t
+
+    def dgrad(conv, dz, h, w, cop, ldz, cin, k, wd=None):
+        if wd is None:
+            wd = prepared[conv]['wd']
+        dx = _new(dev, B, h, w, cin)
+        _gen_conv(L, st, dz, wd, dx, B, h, w, cop, ldz, cin, k, 1, k - 1 - (k - 1) // 2)
+        return dx
+
+    def bn_sums(bn, C):
+        nonlocal off
+        t = sums_arena[off:off + 2 * C]
+        affine.append((bn.bias, off, C))
+        affine.append((bn.weight, off + C, C))
+        off += 2 * C
+        return t
+
+    for op in reversed(dops):
+        h, w = op.h, op.w
+        if op.kind == 'grow':
+            # 3x3: weight gradient from (a2, gradient of the slab), data gradient -> gradient of a2 (kept on the op for the 'pre' op in front of it)
+            gb = gbuf_of(op)
+            dslab = gb.view(-1)[op.out_off:]
+            n1, g = op.K, op.N
+            dwp = _hip.conv_wgrad(op.a2, dslab, B, h, w, n1, n1, g, op.ld, 3)
+            dw = dest(op.conv.weight)
+            _hip.check(L.y2_unpack_weight_grad(_hip.ptr(dwp), _hip.ptr(dw), g, n1, 3, st), 'y2_unpack_weight_grad')
+            ready(op.conv.weight, dw)
+            op.z = dgrad(op.conv, dslab, h, w, g, op.ld, n1, 3)
+            grow = op
+            continue
+        ho, wo = (h // 2, w // 2) if op.pool else (h, w)
+        K, N = op.K, op.N
+        if op.role == 'head':
+            # bias + no activation (has_bn = 0: dz = dout, sums = d bias), written zero-padded to a multiple of 4 channels for the GEMM kernels
+            cop, dz, dwp, wsrc = head_cop, head_dz, head_dwp, head_w
+            bsum = sums_arena[total:total + 2 * N]
+            _hip.check(L.y2_bn_act_bwd_ex(_hip.ptr(op.z), None, _hip.ptr(_hip.f32c(op.conv.bias.detach())), None, None, None, 1.0, _hip.ptr(_hip.f32c(dout)), N, 0, 0,
+                                          None, 0, 0, None, 0, None, 0, None, 0, _hip.ptr(bsum), _hip.ptr(dz), cop, B, ho, wo, N, N, 0, st), 'y2_bn_act_bwd_ex')
+            affine.append((op.conv.bias, total, N))
+            ldz = cop
+            wsrc[:N] = _hip.f32c(op.conv.weight.detach())
+            wd = _new(dev, wsrc.numel())
+            _hip.check(L.y2_pack_weight(_hip.ptr(wsrc), _hip.ptr(wd), cop, K, 1, 1, st), 'y2_pack_weight')
+        elif op.role == 'trans':
+            cop, wd = N, None
+            nb = [o for o in dops if o.kind == 'pre' and o.buf is op.out][0]
+            dz = gbuf_of(nb)          # the first N channels of the next block's gradient buffer
+            ldz = op.out_ld
+            dwp = wbuf[id(op)].view(-1)
+        else:
+            # norm2 + ReLU between the 1x1 and the 3x3: gradient of a2 (from the 'grow' op) -> gradient of the raw 1x1 output
+            cop, wd, ldz = N, None, N
+            dz = _new(dev, B, h, w, N)
+            _hip.check(L.y2_bn_act_bwd_ex(_hip.ptr(op.z), _hip.ptr(op.scale2), _hip.ptr(op.shift2), _hip.ptr(op.mean2), _hip.ptr(op.invstd2),
+                                          _hip.ptr(op.bn2.weight.detach()), 0.0, _hip.ptr(grow.z), N, 0, 0, None, 0, 0, None, 0, None, 0, None, 0,
+                                          _hip.ptr(bn_sums(op.bn2, N)), _hip.ptr(dz), N, B, h, w, N, N, has_bn, st), 'y2_bn_act_bwd_ex')
+            grow.z = None
+            dwp = wbuf[id(op)].view(-1)
+        # 1x1 weight gradient from the recomputed pre-activated operand
+        act = _new(dev, B, ho, wo, K)
+        _hip.check(L.y2_preact_fwd(_hip.ptr(op.buf), _hip.ptr(op.scale), _hip.ptr(op.shift), op.pre_slope, _hip.ptr(act), B, h, w, K, op.ld, K, op.pool, st), 'y2_preact_fwd')
+        _hip.check(L.y2_conv_wgrad_ex(_hip.ptr(act), _hip.ptr(dz), _hip.ptr(dwp), B, ho, wo, K, K, cop, ldz, 1, 1, 0, st), 'y2_conv_wgrad_ex')
+        if op.role == 'head':
+            ready(op.conv.weight, dwp.view(cop, K, 1, 1)[:N].contiguous())
+        else:
+            ready(op.conv.weight, wbuf[id(op)])
+        dA = dgrad(op.conv, dz, ho, wo, cop, ldz, K, 1, wd=wd)
+        _hip.check(L.y2_preact_bwd(_hip.ptr(op.buf), _hip.ptr(op.scale), _hip.ptr(op.shift), op.pre_slope, _hip.ptr(op.mean), _hip.ptr(op.invstd),
+                                   _hip.ptr(op.bn.weight.detach()), _hip.ptr(dA), K, _hip.ptr(bn_sums(op.bn, K)), _hip.ptr(gbuf_of(op)), op.ld,
+                                   1 if op.role == 'layer' else 0, B, h, w, K, op.ld, op.pool, has_bn, st), 'y2_preact_bwd')
+        op.z = op.a2 = None
+    # ---- affine-parameter gradients: fp64 sums -> fp32, one launch
+    items, handed, gb_all = [], [], None
+    for prm, o, ln in affine:
+        t = buffer_hook(prm) if buffer_hook is not None else None
+        if t is None:
+            if gb_all is None:
+                gb_all = _new(dev, sums_arena.numel())
+                items.append((_hip.MULTI_F64_TO_F32, gb_all, sums_arena))
+            t = gb_all[o:o + ln]
+        else:
+            items.append((_hip.MULTI_F64_TO_F32, t, sums_arena[o:o + ln]))
+        handed.append((prm, t))
+    for i in range(0, len(items), 64):
+        _hip.multi(items[i:i + 64], st)
+    for prm, t in handed:
+        ready(prm, t)
+    # ---- gradient of the stem's pooled output: the first c0 channels of block 1's gradient buffer
+    first = dops[0]
+    c0 = dense['c0']
+    dpool = _new(dev, *dense['pooled'].shape)
+    gb = gbufs[id(first.buf)]
+    _hip.check(L.y2_bn_act_fwd(_hip.ptr(gb), None, None, 1.0, _hip.ptr(dpool), None, B, first.h, first.w, c0, first.ld, c0, 0, 0, 0, 0, st), 'y2_bn_act_fwd')
+    ctx.dense = None
+    return dpool
+
+
 def _gen_conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, stride, pad, stats=None, transposed=False, out_hw=None):
     p = _hip.ConvParams()
     p.x, p.w, p.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
@@ -1299,6 +1566,17 @@ class ResNetTrainFn(torch.autograd.Function):
             ctx.net, ctx.ops, ctx.B = net, ops, B
             ctx.param_ids = [id(p) for p in params]
             return cur
+        from model import densenet as _densenet
+        ctx.dense = None
+        if isinstance(net, _densenet.DenseNet):
+            def take_stats(C):
+                t = arena[used[0]:used[0] + _hip.STATS_REPL * 2 * C]
+                used[0] += _hip.STATS_REPL * 2 * C
+                return t
+            out = _densenet_fwd(ctx, net, L, st, dev, B, H, W, x4, cpad, frozen, take_stats, prepared, conv_bn, maxpool)
+            ctx.net, ctx.ops, ctx.B = net, ops, B
+            ctx.param_ids = [id(p) for p in params]
+            return out
         cur, h, w, ld = conv_bn(net.conv1, net.bn1, x4, cpad, H, W, 2, 3, 0.0, first=True)
         cur, h, w = maxpool(cur, h, w, ld, 3, 2, 1, 1)
         for layer in (net.layer1, net.layer2, net.layer3, net.layer4):
@@ -1339,6 +1617,8 @@ class ResNetTrainFn(torch.autograd.Function):
         def dest(param):
             t = buffer_hook(param) if buffer_hook is not None else None
             return t if t is not None else _new(dev, *param.shape)
+        if getattr(ctx, 'dense', None) is not None:
+            dout = _densenet_bwd(ctx, dout, ready, dest, buffer_hook)          # leaves the stem ops (conv0 + norm0 + ReLU, max-pool) to the walk below
         convs = [op for op in ops if op.kind in ('conv', 'dw')]
         # everything that must start from zero, filled by ONE launch: the fp64 sums of every BatchNorm backward, the accumulation targets of the
         # direct (split, atomically added) weight gradients, the zero-padded gradient of the 425-wide head

@@ -572,6 +572,7 @@ class StepRunner(object):
 
     def eligible(self, data):
         import _hip
+        from model import densenet as _densenet
         from model import mobilenet as _mobilenet
         from model import resnet as _resnet
         from model import train_graph
@@ -580,7 +581,7 @@ class StepRunner(object):
         dnn = getattr(inf, 'dnn', None)
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[-1] % 32 or x.shape[-2] % 32:
             return False
-        if not isinstance(inf, model.Inference) or not isinstance(dnn, (_yolo2.Darknet, _resnet.ResNet, _mobilenet.MobileNet)) or not (inf.training and dnn.training):
+        if not isinstance(inf, model.Inference) or not isinstance(dnn, (_yolo2.Darknet, _resnet.ResNet, _mobilenet.MobileNet, _densenet.DenseNet)) or not (inf.training and dnn.training):
             return False
         if _hip.DETERMINISTIC or train_graph.DEBUG_TAP is not None or not torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing():
             return False
