@@ -678,6 +678,13 @@ def _darknet_bwd(ctx, dout):
                 _hip.check(L.y2_unpack_weight_grad(_hip.ptr(dwp), _hip.ptr(dw4), cop, 4, k, st_w), 'y2_unpack_weight_grad')
                 return dw4[:e.cout_r, :cin].contiguous()
             tgt, final, zeroed = wg[i][:3]
+            if not zeroed and wg[i][3] is None:
+                # The algorithm of this shape was unmeasured when the step's zero fill was planned, so the target was left out of it - and an earlier
+                # layer of the SAME shape may have measured "direct" (which accumulates) since.  conv_wgrad's own fill runs on torch's current stream,
+                # the main stream here, unordered against the accumulating kernel on the side stream (seen as a garbage gradient of the second layer
+                # of a shape in the first backward of a process): fill on the stream the weight gradient runs on.
+                _hip.multi([(_hip.MULTI_ZERO, tgt, None)], st_w)
+                zeroed = True
             dw = None
             if k == 3:
                 dw = dest(weight) if (cop == cout and not e.padded) else _new(dev, cop, cin, k, k)
