@@ -282,6 +282,24 @@ int y2_expand_classes(const float* iou, const float* prob, const float* yx_min, 
 int y2_iou_rowmax(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2, int32_t N1, int32_t N2, float min_union,
                   float* best, long long* which, y2_stream_t stream);
 
+/* The matching loop of the VOC evaluation (eval.py:278-292 with filter_valid :140-145, filter_cls_data / filter_cls_pred :148-162, matching and
+ * _matching :57-75) for a batch of B images in ONE launch (one workgroup per image) - in place of one y2_iou_rowmax launch, two blocking copies and
+ * a host claim loop per (image, predicted class).  A latency kernel: about M x G IoUs per image.
+ * Detections (the batch form of detect.postprocess, detect.expand_batch): det_min / det_max [B][M][2] in (y, x) order, det_cls int64 [B][M],
+ * det_count [B]: row i of image b takes part iff i < det_count[b] (clamped to [0, M]).  Ground truth padded to G boxes per image: gt_min / gt_max
+ * [B][G][2], gt_cls int64 [B][G], gt_difficult uint8 [B][G].  A box is VALID iff ymin < ymax, xmin < xmax and difficult < 1 (zero padding is invalid).
+ * cls_num [C] += the number of valid boxes per class (the caller zeroes it; a class id outside [0, C) is not counted).
+ * tp [B][M] uint8: every row is written.  A participating row of class c takes the maximum IoU (the y2_iou_rowmax arithmetic: same device function,
+ * same min_union clamp) over the valid boxes of class c in array order and its FIRST arg-max; it is positive iff that maximum > threshold (strict,
+ * fp32; never without a valid box of its class); tp = positive and no EARLIER participating row of the image (array order - not score order: the
+ * reference sorts only at the end, across images) is positive with the same arg-max box.  Integer atomics only: bit-reproducible.
+ * M >= 0 unbounded, 0 <= G <= Y2_EVAL_MATCH_MAX_G (the image's labels are staged in LDS, 32 bytes per box; more: Y2_ENOSUP, nothing is written).
+ * The det_* / tp pointers may be NULL when M == 0, the gt_* pointers when G == 0. */
+#define Y2_EVAL_MATCH_MAX_G 1024
+int y2_eval_match(const float* det_min, const float* det_max, const long long* det_cls, const int32_t* det_count,
+                  const float* gt_min, const float* gt_max, const long long* gt_cls, const uint8_t* gt_difficult,
+                  int32_t B, int32_t M, int32_t G, int32_t C, float threshold, float min_union, uint8_t* tp, int32_t* cls_num, y2_stream_t stream);
+
 /* batch_iou_matrix: [Bt,N1,2]x2, [Bt,N2,2]x2 -> out [Bt,N1,N2]; iou_matrix is Bt = 1.  min_union = eps32.
  * mode 0: IoU (utils/iou/torch.py:47-61, 139-153);  mode 1: intersection area only (:24-44, 116-136). */
 int y2_iou_matrix(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
@@ -312,6 +330,11 @@ int y2_iou_matrix_host(const float* yx_min1, const float* yx_max1, const float* 
                        int Bt, int N1, int N2, float min_union, int mode, float* out);
 int y2_iou_pair_host(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
                      int n, float min_union, float* out);
+/* y2_eval_match on host memory (eval.match_batch on CPU tensors): the same semantics, the same fp32 IoU sequence, the same G cap - tp and
+ * cls_num are bit-identical to the device entry point. */
+int y2_eval_match_host(const float* det_min, const float* det_max, const long long* det_cls, const int32_t* det_count,
+                       const float* gt_min, const float* gt_max, const long long* gt_cls, const uint8_t* gt_difficult,
+                       int32_t B, int32_t M, int32_t G, int32_t C, float threshold, float min_union, uint8_t* tp, int32_t* cls_num);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic mode (opt-in, process-global; one process per GPU, one stream).  By default the split-K weight gradient, the

@@ -111,6 +111,20 @@ __device__ __forceinline__ uint32_t y2_div(uint32_t n, const y2_fastdiv& f) {
     return (t + ((n - t) >> 1)) >> f.sh;
 }
 
+// ---- IoU of two (y, x) min / max boxes, shared by detect.hip (IoU matrix, NMS, y2_iou_rowmax) and evalmatch.hip (y2_eval_match): one definition,
+// so the batched matcher cannot drift from the per-class one.  Every operation is a separate fp32 rounding (the files are built with -ffp-contract=off).
+// utils/iou/torch.py:34-44,47-61 operation order.
+__device__ __forceinline__ float iou_one(float ymin1, float xmin1, float ymax1, float xmax1,
+                                         float ymin2, float xmin2, float ymax2, float xmax2, float min_union) {
+    const float ih = fmaxf(fminf(ymax1, ymax2) - fmaxf(ymin1, ymin2), 0.f);
+    const float iw = fmaxf(fminf(xmax1, xmax2) - fmaxf(xmin1, xmin2), 0.f);
+    const float inter = ih * iw;
+    const float a1 = (ymax1 - ymin1) * (xmax1 - xmin1);
+    const float a2 = (ymax2 - ymin2) * (xmax2 - xmin2);
+    const float uni = fmaxf((a1 + a2) - inter, min_union);
+    return inter / uni;
+}
+
 #include <stdlib.h>
 // Tile grid of the 4x4-tile forms.  Per image, a map of H rows takes ceil(H / 4) tile rows: 13 rows pay for 16 (the 13x13 layers at 416x416: 34 % of the
 // multiply-adds of their 36 GEMMs are spent on rows and columns that do not exist).  "Mosaic" tiling lays the batch's images out as ONE image - gy rows of gx

@@ -184,17 +184,7 @@ __global__ __launch_bounds__(256) void expand_classes_kernel(const ExpandArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ IoU
-// utils/iou/torch.py:34-44,47-61 operation order; every op is a separate fp32 rounding.
-__device__ __forceinline__ float iou_one(float ymin1, float xmin1, float ymax1, float xmax1,
-                                         float ymin2, float xmin2, float ymax2, float xmax2, float min_union) {
-    const float ih = fmaxf(fminf(ymax1, ymax2) - fmaxf(ymin1, ymin2), 0.f);
-    const float iw = fmaxf(fminf(xmax1, xmax2) - fmaxf(xmin1, xmin2), 0.f);
-    const float inter = ih * iw;
-    const float a1 = (ymax1 - ymin1) * (xmax1 - xmin1);
-    const float a2 = (ymax2 - ymin2) * (xmax2 - xmin2);
-    const float uni = fmaxf((a1 + a2) - inter, min_union);
-    return inter / uni;
-}
+// iou_one (common.h): utils/iou/torch.py:34-44,47-61 operation order, shared with evalmatch.hip.
 
 // eval.py:67-75: per prediction the best IoU over the ground-truth boxes and its index (first maximum, like torch.max over the IoU matrix).
 __global__ __launch_bounds__(256) void iou_rowmax_kernel(const float* __restrict__ mn1, const float* __restrict__ mx1, const float* __restrict__ mn2, const float* __restrict__ mx2,

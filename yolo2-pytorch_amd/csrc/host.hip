@@ -1,4 +1,5 @@
-// host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host).
+// host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
+// y2_eval_match_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -17,7 +18,7 @@
 namespace {
 
 inline float iou_host(float ymin1, float xmin1, float ymax1, float xmax1, float ymin2, float xmin2, float ymax2, float xmax2, float min_union) {
-    // utils/iou/torch.py:34-61 (same operation order as detect.hip: iou_one)
+    // utils/iou/torch.py:34-61 (same operation order as common.h: iou_one)
     const float ih = fmaxf(fminf(ymax1, ymax2) - fmaxf(ymin1, ymin2), 0.f);
     const float iw = fmaxf(fminf(xmax1, xmax2) - fmaxf(xmin1, xmin2), 0.f);
     const float inter = ih * iw;
@@ -108,5 +109,50 @@ extern "C" int y2_iou_pair_host(const float* mn1, const float* mx1, const float*
     if (!mn1 || !mx1 || !mn2 || !mx2 || !out) return Y2_EINVAL;
     for (int i = 0; i < n; ++i)
         out[i] = iou_host(mn1[2 * i], mn1[2 * i + 1], mx1[2 * i], mx1[2 * i + 1], mn2[2 * i], mn2[2 * i + 1], mx2[2 * i], mx2[2 * i + 1], min_union);
+    return Y2_OK;
+}
+
+// eval.py:278-292 for a batch (evalmatch.hip: eval_match_kernel, serially): per image the valid boxes are counted per class, every participating row takes
+// its best valid same-class box (first maximum) and the EARLIEST positive row per box is the true positive.
+extern "C" int y2_eval_match_host(const float* det_min, const float* det_max, const long long* det_cls, const int32_t* det_count,
+                                  const float* gt_min, const float* gt_max, const long long* gt_cls, const uint8_t* gt_difficult,
+                                  int B, int M, int G, int C, float threshold, float min_union, uint8_t* tp, int32_t* cls_num) {
+    if (B <= 0 || M < 0 || G < 0 || C <= 0 || !det_count || !cls_num) return Y2_EINVAL;
+    if (M > 0 && (!det_min || !det_max || !det_cls || !tp)) return Y2_EINVAL;
+    if (G > 0 && (!gt_min || !gt_max || !gt_cls || !gt_difficult)) return Y2_EINVAL;
+    if (G > Y2_EVAL_MATCH_MAX_G) return Y2_ENOSUP;
+    std::vector<uint8_t> valid((size_t)G), claimed((size_t)G);
+    for (int b = 0; b < B; ++b) {
+        const size_t g0 = (size_t)b * G, d0 = (size_t)b * M;
+        for (int g = 0; g < G; ++g) {
+            const size_t o = g0 + g;
+            const bool v = gt_min[2 * o] < gt_max[2 * o] && gt_min[2 * o + 1] < gt_max[2 * o + 1] && gt_difficult[o] < 1;
+            valid[(size_t)g] = v;
+            claimed[(size_t)g] = 0;
+            const long long c = gt_cls[o];
+            if (v && c >= 0 && c < C) cls_num[c] += 1;
+        }
+        int count = det_count[b];
+        count = count < 0 ? 0 : (count > M ? M : count);
+        for (int i = 0; i < M; ++i) {
+            const size_t o = d0 + i;
+            tp[o] = 0;
+            if (i >= count) continue;
+            const long long c = det_cls[o];
+            float bv = 0.f;
+            int bi = -1;
+            for (int g = 0; g < G; ++g) {
+                if (!valid[(size_t)g] || gt_cls[g0 + g] != c) continue;
+                const size_t q = g0 + g;
+                const float v = iou_host(det_min[2 * o], det_min[2 * o + 1], det_max[2 * o], det_max[2 * o + 1],
+                                         gt_min[2 * q], gt_min[2 * q + 1], gt_max[2 * q], gt_max[2 * q + 1], min_union);
+                if (bi < 0 || v > bv) { bv = v; bi = g; }
+            }
+            if (bi >= 0 && bv > threshold && !claimed[(size_t)bi]) {        // rows in ascending order: the first positive row of a box claims it
+                claimed[(size_t)bi] = 1;
+                tp[o] = 1;
+            }
+        }
+    }
     return Y2_OK;
 }

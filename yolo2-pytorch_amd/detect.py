@@ -141,6 +141,25 @@ def postprocess_batch(d, fix=False, threshold_cls=0.005, to_host=False):
     return out
 
 
+def expand_batch(d, fix=False, threshold_cls=0.005):
+    """The batch form of postprocess_batch for consumers that stay on the device (eval.match_batch): the result buffers of a detect_batch result
+    as a dict of device tensors - yx_min / yx_max [B,M,2], cls int64 [B,M], score [B,M], count int32 [B] - with NO host synchronisation.  Rows
+    [0, count[b]) of image b are what postprocess_batch returns for it, in values and order; the rows behind them are not meaningful.
+    fix: M = limit * C (the expanded detections); otherwise M = limit (the NMS survivors with their arg-max class).
+    Every returned tensor is allocated by this call (count too: without `fix` it is a copy of d['keep_count'], an asynchronous device copy), so a
+    consumer may keep the dict while `d` - the static result of a GraphedDetector, say - is overwritten by the next batch."""
+    keep = d['keep']
+    B, limit = keep.shape
+    n = d['iou'].numel() // B
+    k_iou, k_min, k_max, e_min, e_max, e_score, e_cls, e_count = _expand(d['iou'].view(B, n), d['prob'].view(B, n, -1), d['yx_min'].view(B, n, 2), d['yx_max'].view(B, n, 2),
+                                                                        d['index'], keep, d['keep_count'], fix, threshold_cls)
+    if fix:
+        return dict(yx_min=e_min, yx_max=e_max, cls=e_cls, score=e_score, count=e_count)
+    # cls[b, k] = cls[b, index[b, keep[b, k]]]: keep beyond keep_count (and index beyond count) is whatever the buffers held - clamped, so that no gather leaves its row
+    src = d['index'].long().gather(1, keep.long().clamp_(0, n - 1)).clamp_(0, n - 1)
+    return dict(yx_min=k_min, yx_max=k_max, cls=d['cls'].view(B, n).long().gather(1, src), score=k_iou, count=d['keep_count'].clone())
+
+
 class GraphedDetector(object):
     """hipGraph capture of the whole device-resident detect step (conv stack + decode + filter + NMS, ~30 launches) for a
     fixed input shape: one graph launch per batch instead of ~30 kernel launches and ~40 tensor allocations from Python.
