@@ -300,6 +300,26 @@ int y2_eval_match(const float* det_min, const float* det_max, const long long* d
                   const float* gt_min, const float* gt_max, const long long* gt_cls, const uint8_t* gt_difficult,
                   int32_t B, int32_t M, int32_t G, int32_t C, float threshold, float min_union, uint8_t* tp, int32_t* cls_num, y2_stream_t stream);
 
+/* The collate step of the data pipeline (utils/data.py:114-133: cv2.resize of the cropped, possibly flipped image - transform/resize/label.py:25-74,
+ * transform/augmentation.py:88-103 - then BGR2RGB, ToTensor, Normalize) for a ragged batch of uint8 images in ONE launch.
+ * src: one packed byte buffer; image b starts at src + offset[b] (any byte alignment), 3 interleaved channels per pixel.
+ * geom [B][8] int32: {row_stride_bytes, src_h, src_w, win_y0, win_x0, win_h, win_w, flip}.  The window is in the frame AFTER the optional horizontal
+ * flip: with flip set, frame column x is source column src_w - 1 - x.  The whole image without flip is the reference's `rescale`.
+ * lut [3][256] fp32, indexed by OUTPUT plane: the whole of ToTensor + Normalize (or any per-level map) as a table; no arithmetic on levels follows
+ * the resize.  flags bit 0: output plane c reads source channel 2 - c (BGR2RGB).  out [B][3][H][W] fp32 (what y2_conv0_fwd / y2_nchw_to_nhwc read).
+ * Resampling (per axis, window extent s -> output extent d, 8-bit INTER_LINEAR arithmetic): scale = (double)s / d;
+ * f = (float)((i + 0.5) * scale - 0.5), k = floor(f), f -= k; horizontally only: k < 0 -> k = 0, f = 0 and k >= s - 1 -> k = s - 1, f = 0; taps
+ * clamp(k, 0, s - 1) and clamp(k + 1, 0, s - 1); c1 = rint(f * 2048.f), c0 = rint((1.f - f) * 2048.f).  h = p0 * c0 + p1 * c1 per source row,
+ * level = clamp((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2, 0, 255).  When win_h == 2 * H AND win_w == 2 * W the level is the
+ * 2x2 box mean (a + b + c + d + 2) >> 2.  Integer after the coefficients: bit-identical on device and host.
+ * B == 0: nothing is launched.  W <= Y2_COLLATE_MAX_W (the column taps are staged in LDS; more: Y2_EINVAL).  16-byte stores when W % 4 == 0 and
+ * out is 16-byte aligned, 4-byte stores otherwise.  Never allocates, never synchronises.  The tables are DEVICE memory: the device entry point
+ * cannot check a window against src_h / src_w (utils.data.to_device and the host function do); it only keeps every tap inside the image the
+ * table names. */
+#define Y2_COLLATE_MAX_W 4096
+int y2_collate_images(const uint8_t* src, const int64_t* offset, const int32_t* geom, const float* lut,
+                      int32_t B, int32_t H, int32_t W, int32_t flags, float* out, y2_stream_t stream);
+
 /* batch_iou_matrix: [Bt,N1,2]x2, [Bt,N2,2]x2 -> out [Bt,N1,N2]; iou_matrix is Bt = 1.  min_union = eps32.
  * mode 0: IoU (utils/iou/torch.py:47-61, 139-153);  mode 1: intersection area only (:24-44, 116-136). */
 int y2_iou_matrix(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
@@ -335,6 +355,10 @@ int y2_iou_pair_host(const float* yx_min1, const float* yx_max1, const float* yx
 int y2_eval_match_host(const float* det_min, const float* det_max, const long long* det_cls, const int32_t* det_count,
                        const float* gt_min, const float* gt_max, const long long* gt_cls, const uint8_t* gt_difficult,
                        int32_t B, int32_t M, int32_t G, int32_t C, float threshold, float min_union, uint8_t* tp, int32_t* cls_num);
+/* y2_collate_images on host memory (utils.data.to_device on 'cpu'): the same arithmetic, bit-identical output.  The tables are checked first
+ * (offset >= 0, row_stride_bytes >= 3 * src_w, the window inside the image, flip 0 or 1): Y2_EINVAL, nothing is written. */
+int y2_collate_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const float* lut,
+                           int32_t B, int32_t H, int32_t W, int32_t flags, float* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic mode (opt-in, process-global; one process per GPU, one stream).  By default the split-K weight gradient, the

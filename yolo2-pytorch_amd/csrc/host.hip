@@ -1,5 +1,5 @@
 // host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
-// y2_eval_match_host).
+// y2_eval_match_host, y2_collate_images_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -29,6 +29,23 @@ inline float iou_host(float ymin1, float xmin1, float ymax1, float xmax1, float 
 }
 
 inline float nms_key(float s) { return s != s ? -INFINITY : s; }   // NaN ranks last (detect.hip: nms_key)
+
+// collate.hip: cl_axis, operation for operation (exactly rounded IEEE operations only: the device gives the same bits)
+inline void collate_axis(int i, int s, int d, bool edge, int& k, int& c0, int& c1) {
+    const double scale = (double)s / (double)d;
+    float f = (float)(((double)i + 0.5) * scale - 0.5);
+    const float fl = floorf(f);
+    k = (int)fl;
+    f -= fl;
+    if (edge) {
+        if (k < 0) { k = 0; f = 0.f; }
+        if (k >= s - 1) { k = s - 1; f = 0.f; }
+    }
+    c1 = (int)rintf(f * 2048.f);
+    c0 = (int)rintf((1.f - f) * 2048.f);
+}
+
+inline int collate_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 }  // namespace
 
@@ -151,6 +168,64 @@ extern "C" int y2_eval_match_host(const float* det_min, const float* det_max, co
             if (bi >= 0 && bv > threshold && !claimed[(size_t)bi]) {        // rows in ascending order: the first positive row of a box claims it
                 claimed[(size_t)bi] = 1;
                 tp[o] = 1;
+            }
+        }
+    }
+    return Y2_OK;
+}
+
+// y2_collate_images on host memory (collate.hip: collate_images_kernel, serially).  The tables are readable here, so they are checked before
+// anything is written: a window outside its image is Y2_EINVAL.
+extern "C" int y2_collate_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const float* lut,
+                                      int32_t B, int32_t H, int32_t W, int32_t flags, float* out) {
+    if (B < 0 || H <= 0 || W <= 0 || W > Y2_COLLATE_MAX_W || (flags & ~1)) return Y2_EINVAL;
+    if (B == 0) return Y2_OK;
+    if (B > 65535) return Y2_ENOSUP;
+    if (!src || !offset || !geom || !lut || !out) return Y2_EINVAL;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* g = geom + 8 * (size_t)b;
+        const long long stride = g[0], src_h = g[1], src_w = g[2], wy0 = g[3], wx0 = g[4], wh = g[5], ww = g[6];
+        if (offset[b] < 0 || src_h < 1 || src_w < 1 || stride < 3 * src_w || wh < 1 || ww < 1 || wy0 < 0 || wx0 < 0 || wy0 + wh > src_h || wx0 + ww > src_w
+            || (g[7] != 0 && g[7] != 1))
+            return Y2_EINVAL;
+    }
+    const int cs = (flags & 1) ? 2 : 0;
+    const size_t plane = (size_t)H * W;
+    std::vector<int> off0((size_t)W), off1((size_t)W), xc0((size_t)W), xc1((size_t)W);
+    for (int b = 0; b < B; ++b) {
+        const int32_t* g = geom + 8 * (size_t)b;
+        const int stride = g[0], src_w = g[2], wy0 = g[3], wx0 = g[4], wh = g[5], ww = g[6], flip = g[7];
+        const bool box = wh == 2 * H && ww == 2 * W;
+        for (int x = 0; x < W; ++x) {
+            int k, c0, c1;
+            if (box) { k = 2 * x; c0 = c1 = 0; }
+            else collate_axis(x, ww, W, true, k, c0, c1);
+            int s0 = wx0 + collate_clamp(k, 0, ww - 1), s1 = wx0 + collate_clamp(k + 1, 0, ww - 1);
+            if (flip) { s0 = src_w - 1 - s0; s1 = src_w - 1 - s1; }
+            off0[(size_t)x] = 3 * s0; off1[(size_t)x] = 3 * s1; xc0[(size_t)x] = c0; xc1[(size_t)x] = c1;
+        }
+        const uint8_t* img = src + offset[b];
+        float* o = out + (size_t)b * 3 * plane;
+        for (int y = 0; y < H; ++y) {
+            int k, b0, b1;
+            if (box) { k = 2 * y; b0 = b1 = 0; }
+            else collate_axis(y, wh, H, false, k, b0, b1);
+            const uint8_t* p0 = img + (long long)(wy0 + collate_clamp(k, 0, wh - 1)) * stride;
+            const uint8_t* p1 = img + (long long)(wy0 + collate_clamp(k + 1, 0, wh - 1)) * stride;
+            for (int c = 0; c < 3; ++c) {
+                const int ch = c == 1 ? 1 : c ^ cs;
+                float* row = o + c * plane + (size_t)y * W;
+                for (int x = 0; x < W; ++x) {
+                    const int o0 = off0[(size_t)x] + ch, o1 = off1[(size_t)x] + ch;
+                    int level;
+                    if (box) level = ((int)p0[o0] + (int)p0[o1] + (int)p1[o0] + (int)p1[o1] + 2) >> 2;
+                    else {
+                        const int h0 = (int)p0[o0] * xc0[(size_t)x] + (int)p0[o1] * xc1[(size_t)x];
+                        const int h1 = (int)p1[o0] * xc0[(size_t)x] + (int)p1[o1] * xc1[(size_t)x];
+                        level = collate_clamp((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2, 0, 255);
+                    }
+                    row[x] = lut[c * 256 + level];
+                }
             }
         }
     }

@@ -1,0 +1,172 @@
+"""`utils.data` — the collate step of the reference's data pipeline (utils/data.py:29-42, 93-141), split at the process boundary.
+
+`Collate` runs in DataLoader worker processes, which must not touch the GPU: it chooses the batch's size (`next_size`: the reference's schedule), runs the
+resize transform on the LABELS (transform.resize.label: the geometry is recorded, no pixel is touched), pads the labels (`padding_labels`) with
+zero rows and packs the untouched uint8 images into one byte buffer with an offset and a geometry row per image.  It returns no `tensor`.
+`to_device` runs in the main process: at most one copy per tensor, then ONE y2_collate_images launch (crop, flip, resize, channel swap, ToTensor +
+Normalize as a table) writes `batch['tensor']`, the fp32 [B,3,H,W] input of the network.  On 'cpu' it runs y2_collate_images_host, the
+bit-identical host function.
+
+What ships to the device is the source pixels as cv2.imread returned them - a quarter to a third of the bytes of the finished fp32 tensor."""
+import os
+import pickle
+import random
+
+import numpy as np
+import torch
+
+import _hip
+
+LABELS = 'yx_min, yx_max, cls, difficult'.split(', ')
+
+
+def padding_labels(data, dim, labels=LABELS):
+    """The labels of one sample as arrays of `dim` boxes: the sample's own boxes first, zero rows behind them (the reference's helper of this name)."""
+    for key in labels:
+        label = data[key]
+        padded = np.zeros((dim,) + label.shape[1:], label.dtype)
+        padded[:len(label)] = label
+        data[key] = padded
+    return data
+
+
+def check_geometry(offset, geom, nbytes):
+    """The tables of y2_collate_images against the byte buffer they index (host arrays): every image inside the buffer, every window inside its image."""
+    offset, geom = np.asarray(offset, np.int64), np.asarray(geom, np.int64)
+    if geom.ndim != 2 or geom.shape[1] != 8 or offset.shape != (geom.shape[0],):
+        raise ValueError('collate: offset must be [B] and geom [B, 8] (got %s and %s)' % (offset.shape, geom.shape))
+    stride, src_h, src_w, y0, x0, h, w, flip = geom.T
+    bad = ((offset < 0) | (src_h < 1) | (src_w < 1) | (stride < 3 * src_w) | (h < 1) | (w < 1) | (y0 < 0) | (x0 < 0) | (y0 + h > src_h) | (x0 + w > src_w)
+           | ((flip != 0) & (flip != 1)) | (offset + (src_h - 1) * stride + 3 * src_w > nbytes))
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError('collate: image %d: window or image outside its buffer (offset %d of %d bytes, geom %s)' % (b, offset[b], nbytes, geom[b].tolist()))
+
+
+class Collate(object):
+    """The worker-process half of the collate step, with the constructor and the size schedule of the reference's class of this name.
+    resize: transform.resize.label.Rescale / Resize / RandomCrop, called as resize(data, height, width): resizes the labels, records the geometry.
+    sizes: the (height, width) pairs a batch's size is drawn from with random.choice; a drawn size serves `maintain` further batches.
+    swap_rb: the images are BGR (cv2.imread) and the network reads RGB (transform.image.BGR2RGB).
+    normalize: (mean, std) of transform.image.Normalize after ToTensor; None: ToTensor only.
+    dir: where the sample that raised is pickled before the exception goes on."""
+
+    def __init__(self, resize, sizes, maintain=1, swap_rb=True, normalize=(0.5, 1.0), dir=None):
+        if maintain <= 0:
+            raise ValueError('Collate: maintain must be positive')
+        self.resize, self.sizes, self.maintain, self.dir = resize, sizes, maintain, dir
+        self.swap_rb = bool(swap_rb)
+        self.normalize = None if normalize is None else (float(normalize[0]), float(normalize[1]))
+        self._repeats_left = 0
+
+    def next_size(self):
+        if self._repeats_left == 0:
+            self.size = random.choice(self.sizes)
+            self._repeats_left = self.maintain
+        else:
+            self._repeats_left -= 1
+        return self.size
+
+    def _prepare(self, data, height, width, dim):
+        data = padding_labels(self.resize(data, height, width), dim)
+        image = data['image']
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError('collate: an image must be uint8 [h, w, 3] (got %s %s)' % (image.dtype, image.shape))
+        return data
+
+    def _keep(self, data):
+        if self.dir is not None:
+            os.makedirs(self.dir, exist_ok=True)
+            with open(os.path.join(self.dir, '%s.%s.pkl' % (type(self).__module__, type(self).__name__)), 'wb') as f:
+                pickle.dump(data, f)
+
+    def __call__(self, batch):
+        height, width = self.next_size()
+        dim = max(len(data['cls']) for data in batch)
+        samples = []
+        for data in batch:
+            try:
+                samples.append(self._prepare(data, height, width, dim))
+            except Exception:
+                self._keep(data)
+                raise
+        out = {key: torch.from_numpy(np.stack([data[key] for data in samples])) for key in LABELS}      # (what default_collate makes of numpy arrays)
+        offset = np.zeros(len(samples), np.int64)
+        geom = np.zeros((len(samples), 8), np.int32)
+        pos = 0
+        for b, data in enumerate(samples):
+            h, w = data['image'].shape[:2]
+            offset[b] = pos
+            geom[b] = (3 * w, h, w) + tuple(data['window']) + (int(bool(data['flip'])),)
+            pos += 3 * h * w
+        raw = np.empty(pos, np.uint8)
+        for b, data in enumerate(samples):
+            raw[offset[b]:offset[b] + data['image'].size] = data['image'].reshape(-1)
+        check_geometry(offset, geom, pos)
+        out.update(raw=torch.from_numpy(raw), offset=torch.from_numpy(offset), geom=torch.from_numpy(geom), size=(height, width),
+                   swap_rb=self.swap_rb, normalize=self.normalize)
+        return out
+
+
+_LUT = {}
+
+
+def level_table(normalize, device):
+    """[3, 256] fp32: ToTensor (`.float().div(255)`) and Normalize (`sub(mean).div(std)`, one mean and std for the three channels:
+    transform/image.py:101-105) of every uint8 level, computed with torch's own operations on the CPU - bit-identical to the reference's per-pixel
+    arithmetic by construction.  Cached per (mean, std, device).  The FIRST call for a key on a GPU copies the table from pageable memory, which
+    blocks the host and cannot be captured: call it (or to_device) once per (normalize, device) before a loop that must not synchronise."""
+    normalize = None if normalize is None else (float(normalize[0]), float(normalize[1]))
+    device = torch.device(device)
+    key = (normalize, str(device))
+    lut = _LUT.get(key)
+    if lut is None:
+        lut = torch.arange(256).float().div(255)
+        if normalize is not None:
+            mean, std = normalize
+            lut = (lut - mean) / std
+        lut = _LUT[key] = lut.view(1, 256).repeat(3, 1).contiguous().to(device)
+    return lut
+
+
+def to_device(batch, device=None, out=None):
+    """The main-process half of the collate step: a copy of `batch` (the dict of Collate) with every tensor on `device` - at most one copy each,
+    non_blocking from pinned memory, no synchronisation once level_table() has met this (normalize, device) - and `tensor` [B,3,H,W] fp32 written by one y2_collate_images launch on the current
+    stream (device 'cpu': y2_collate_images_host).  device=None: where `raw` is when that is a GPU, else the current GPU, else the CPU.
+    `out`: the destination (e.g. the static input buffer of a captured graph) instead of a fresh tensor.  `batch['lut']` ([3,256] fp32), when
+    present, replaces the ToTensor + Normalize table (any per-level map, e.g. a gamma curve).  The tables are checked here while they are host
+    memory; tables that arrive on the device are the caller's."""
+    raw = batch['raw']
+    if device is None:
+        device = raw.device if raw.is_cuda else torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    H, W = (int(v) for v in batch['size'])
+    if not batch['geom'].is_cuda and not batch['offset'].is_cuda:
+        check_geometry(batch['offset'].numpy(), batch['geom'].numpy(), raw.numel())
+    res = {k: (v.to(device, non_blocking=v.is_pinned()) if torch.is_tensor(v) else v) for k, v in batch.items()}
+    raw, offset, geom = res['raw'], res['offset'], res['geom']
+    B = geom.size(0)
+    if raw.dtype != torch.uint8 or offset.dtype != torch.int64 or geom.dtype != torch.int32 or geom.dim() != 2 or geom.size(1) != 8 or offset.numel() != B:
+        raise ValueError('to_device: raw must be uint8, offset int64 [B], geom int32 [B, 8]')
+    if not (0 < W <= _hip.COLLATE_MAX_W and H > 0):
+        raise ValueError('to_device: size %dx%d (the width is limited to %d)' % (H, W, _hip.COLLATE_MAX_W))
+    raw, offset, geom = raw.contiguous(), offset.contiguous(), geom.contiguous()
+    lut = res.get('lut')
+    if lut is None:
+        lut = level_table(batch.get('normalize', (0.5, 1.0)), device)
+    elif lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
+        raise ValueError('to_device: lut must be a contiguous fp32 [3, 256] tensor')
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous() or out.device != device:
+        raise ValueError('to_device: out must be a contiguous fp32 [%d, 3, %d, %d] tensor on %s' % (B, H, W, device))
+    args = (raw.data_ptr(), offset.data_ptr(), geom.data_ptr(), lut.data_ptr(), B, H, W, 1 if batch.get('swap_rb', True) else 0, out.data_ptr())
+    if device.type == 'cuda':
+        with torch.cuda.device(device):
+            _hip.check(_hip.lib().y2_collate_images(*args, _hip.stream()), 'y2_collate_images')
+    else:
+        _hip.check(_hip.lib().y2_collate_images_host(*args), 'y2_collate_images_host')
+    res['tensor'] = out
+    return res
