@@ -165,3 +165,17 @@ def test_step_runner_keeps_one_plan_per_shape_and_degrades_per_shape(monkeypatch
     for _ in range(5):
         assert r.step(batch(224, 6))
     assert made[-1].ops is None and r.captures == 4
+
+
+def test_oplist_builder_selection_names_an_unknown_class():
+    """model.train_oplist picks the builder function by the network's class, in one place; a module of any other class is refused by name
+    before anything is launched."""
+    import torch.nn as nn
+
+    import model.resnet
+    import model.yolo2
+    from model import train_oplist
+    assert train_oplist._builder(object.__new__(model.yolo2.Tiny)) is train_oplist._build_tiny          # (a subclass of Darknet: not Darknet's graph)
+    assert train_oplist._builder(object.__new__(model.resnet.ResNet)) is train_oplist._build_resnet
+    with pytest.raises(TypeError, match=r'no training-graph builder for torch\.nn\.modules\.linear\.Linear'):
+        train_oplist._builder(nn.Linear(1, 1))

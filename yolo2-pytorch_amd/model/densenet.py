@@ -17,7 +17,7 @@ commute) into the next block buffer.  The head is y2_preact_conv1x1_fwd with nor
 bias in the epilogue.  Y2_DENSE_FUSED=0 runs every pre-activated 1x1 as the two-kernel form instead (y2_preact_fwd + 1x1 y2_conv_fwd): the A/B leg
 of tools/densenet_bench.py.  nn.Conv2d / nn.BatchNorm2d are parameter containers only.
 
-Training runs through model/train_graph.py (ResNetTrainFn, DenseNet branch: 'pre' / 'grow' ops): the batch statistics of a slab of the
+Training runs through model/train_oplist.py (OpListTrainFn, _build_densenet: 'pre' / 'grow' ops): the batch statistics of a slab of the
 concatenation are taken once, by its producer, and every consumer's BatchNorm finalises from them; the backward walks a block's layers in reverse
 and accumulates into ONE gradient buffer per block through y2_preact_bwd.  It needs every width to be a multiple of 4.
 """
@@ -371,11 +371,11 @@ class DenseNet(nn.Module):
     def forward(self, x):
         _hip.require_gpu(x)
         if self.training:        # BN semantics follow self.training alone (see model.yolo2.Darknet.forward)
-            from model import train_graph
-            return train_graph.densenet_forward(self, x)
+            from model import train_oplist
+            return train_oplist.forward(self, x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_graph
-            return train_graph.densenet_forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
+            from model import train_oplist
+            return train_oplist.forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
         with torch.no_grad():
             out = self.forward_nhwc(x)
         return out.permute(0, 3, 1, 2)

@@ -11,7 +11,7 @@ Execution (inference): the NCHW input is converted once to zero-padded 4-channel
 depthwise 3x3 is one y2_dwconv_fwd launch (csrc/dwconv.hip) with its folded BatchNorm and ReLU in the epilogue; the head is a 1x1
 y2_conv_fwd with its bias.  Activations carry a pixel stride rounded up to 4 channels (zero padding), so pruned odd widths run in
 inference (the depthwise kernel then takes its scalar path).  nn.Conv2d / nn.BatchNorm2d are parameter containers only.  Training
-runs through model/train_graph.py (ResNetTrainFn, MobileNet branch: batch-statistics BN, depthwise data / weight gradients by
+runs through model/train_oplist.py (OpListTrainFn, _build_mobilenet: batch-statistics BN, depthwise data / weight gradients by
 y2_dwconv_dgrad / y2_dwconv_wgrad); it needs every width to be a multiple of 4.
 """
 import collections
@@ -102,7 +102,7 @@ class MobileNet(nn.Module):
 
     def backward_param_order(self):
         """Convolution weights in the order the training backward finishes their gradients (the reverse of the forward's op list,
-        model.train_graph.ResNetTrainFn: stem, per unit depthwise then pointwise, head)."""
+        model.train_oplist._build_mobilenet: stem, per unit depthwise then pointwise, head)."""
         fwd = [self.stem().conv]
         for _, unit, _ in self.units():
             fwd += [unit.dw.conv, unit.pw.conv]
@@ -275,11 +275,11 @@ class MobileNet(nn.Module):
 
     def forward(self, x):
         if self.training:        # BN semantics follow self.training alone (see model.yolo2.Darknet.forward)
-            from model import train_graph
-            return train_graph.mobilenet_forward(self, x)
+            from model import train_oplist
+            return train_oplist.forward(self, x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_graph
-            return train_graph.mobilenet_forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
+            from model import train_oplist
+            return train_oplist.forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
         with torch.no_grad():
             out = self.forward_nhwc(x)
         return out.permute(0, 3, 1, 2)

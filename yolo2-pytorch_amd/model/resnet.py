@@ -10,8 +10,8 @@ convolution — 7x7/s2 stem, 3x3/s2, 1x1/s2 down-sample, 1x1, 3x3 — is one y2_
 LDS-DMA kernel with BatchNorm folded into the epilogue, ReLU as LeakyReLU(slope 0), and the residual addition of
 BasicBlock / Bottleneck (model/resnet.py:59,101) fused into the epilogue of the block's last convolution; the stem
 max-pool is y2_maxpool_fwd.  The whole chain is one y2_conv_fwd_batch call per stage list, built once per input shape.
-nn.Conv2d / nn.BatchNorm2d objects are parameter containers only.  Training runs through model/train_graph.py
-(ResNetTrainFn: batch-statistics BN, strided data gradients as transposed convolutions, general weight gradient).
+nn.Conv2d / nn.BatchNorm2d objects are parameter containers only.  Training runs through model/train_oplist.py
+(OpListTrainFn, _build_resnet: batch-statistics BN, strided data gradients as transposed convolutions, general weight gradient).
 """
 import ctypes
 import logging
@@ -92,7 +92,7 @@ class ResNet(nn.Module):
 
     def backward_param_order(self):
         """Convolution weights in the order the training backward finishes their gradients (the reverse of the forward's op list,
-        model.train_graph.ResNetTrainFn: stem, per block the projection shortcut then its convolutions, head)."""
+        model.train_oplist._build_resnet: stem, per block the projection shortcut then its convolutions, head)."""
         fwd = [self.conv1]
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
@@ -290,11 +290,11 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         if self.training:        # BN semantics follow self.training alone (see model.yolo2.Darknet.forward)
-            from model import train_graph
-            return train_graph.resnet_forward(self, x)
+            from model import train_oplist
+            return train_oplist.forward(self, x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_graph
-            return train_graph.resnet_forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
+            from model import train_oplist
+            return train_oplist.forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
         with torch.no_grad():
             out = self.forward_nhwc(x)
         return out.permute(0, 3, 1, 2)

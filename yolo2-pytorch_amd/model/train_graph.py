@@ -2,8 +2,9 @@
 
 The reference trains through torch autograd over nn.Conv2d / nn.BatchNorm2d / LeakyReLU / MaxPool2d
 (model/yolo2.py:49-130) and elementwise tensor expressions (model/__init__.py:117-167); `train.py:344-357` calls
-`_inference` -> `loss` -> `backward` -> `optimizer.step`.  Here the same Python surface is kept and three Functions
-carry the arithmetic:
+`_inference` -> `loss` -> `backward` -> `optimizer.step`.  Here the same Python surface is kept.  This module holds the Darknet
+graph, the head and the captured step; the plugins (Tiny, the ResNets, MobileNet, the DenseNets) train through the op-list graph of
+model/train_oplist.py, and both graphs are built from the parts in model/_train_parts.py.  Three Functions carry Darknet's arithmetic:
 
   DarknetTrainFn : x, parameters -> head image (NHWC).  forward = per block {raw conv (+ per-channel sum / sum^2 in the
                    epilogue) -> y2_bn_finalize (batch statistics, running-stat update) -> y2_bn_act_fwd (affine +
@@ -23,6 +24,8 @@ import torch
 import torch.distributed as dist
 
 import _hip
+from model import train_oplist
+from model._train_parts import BN_MOMENTUM, LEAKY, GradSink, StatsArena, _new, bn_params, cached_buf, prep_weights
 
 BWD_STREAMS = int(os.environ.get('Y2_BWD_STREAMS', '2'))     # 2: weight gradients on a side stream (overlap with the HBM-bound passes); 1: one stream
 _SIDE = {}
@@ -63,24 +66,7 @@ def _sum_over_ranks(t, reducer):
     return bool(reducer(t)) if reducer is not None else False
 
 
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.01
-LEAKY = 0.1
 _WINO_CHUNK_BYTES = int(os.environ.get('Y2_WINO_CHUNK_MB', '4096')) << 20      # csrc/wino.hip: wino_chunk_bytes()
-
-
-def _counter(bn):
-    """nn.BatchNorm2d.num_batches_tracked as y2_bn_finalize increments it in place: an int64 scalar on the module's device."""
-    t = bn.num_batches_tracked
-    if t is None:
-        return None
-    if t.dtype != torch.int64 or not t.is_cuda:
-        raise RuntimeError('BatchNorm2d.num_batches_tracked must be an int64 GPU tensor (got %s on %s)' % (t.dtype, t.device))
-    return t
-
-
-def _new(dev, *shape, dtype=torch.float32):
-    return torch.empty(*shape, dtype=dtype, device=dev)
 
 
 OperandPruned = _hip.OperandMissing      # a captured step prepares only the GEMM operands its warm-up passes used (StepPlan.used_last); the algorithm table asked for another one
@@ -188,11 +174,7 @@ def _train_operands(dnn, dev, scope=None, only=None, alloc_only=False):
             dnn._train_bufs = bufs
 
     def buf(tag, n):
-        t = bufs[1].get(tag)
-        if t is None or t.numel() != n or t.device != dev:
-            t = torch.empty(n, dtype=torch.float32, device=dev)
-            bufs[1][tag] = t
-        return t
+        return cached_buf(bufs[1], tag, n, dev)
     first = dnn._first_block()
     items, ops = [], {}
     # the Winograd filter transforms of all layers live in ONE arena: in the split-bf16 mode a single y2_split_bf16x3 pass turns it into
@@ -235,11 +217,7 @@ def _train_operands(dnn, dev, scope=None, only=None, alloc_only=False):
             off += 16 * cout * cin
     if alloc_only:
         return ops
-    if items:
-        table = (_hip.PrepItem * len(items))()
-        for e, (src, dst, cout, cin, k, mode) in zip(table, items):
-            e.src, e.dst, e.Cout, e.Cin, e.ksize, e.mode = src.data_ptr(), dst.data_ptr(), cout, cin, k, mode
-        _hip.check(_hip.lib().y2_prep_weights(table, len(items), _hip.stream()), 'y2_prep_weights')
+    prep_weights(items)
     if usize and _hip.split_mode():
         f16 = _hip.split_mode() == 'f16'
         np_, dt = (2, torch.float16) if f16 else (3, torch.bfloat16)
@@ -365,18 +343,7 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
     eff = _effective(dnn, dev, frozen)
     used = ctx.used = set()          # (block, operand form) pairs this pass's chosen algorithms read: what a captured step has to prepare
     prepared = _train_operands(dnn, dev, (getattr(ctx, 'ops_scope', None) or scope) if scope is not None else None, only=getattr(ctx, 'only', None)) if not any(e.padded for e in eff.values()) else {}
-    det = _hip.ensure_deterministic(dev)      # fixed-order reductions: BN statistics by y2_colstats_det instead of epilogue atomics
-    # one zero-filled arena for every layer's replicated BN-statistics accumulators (one launch instead of 22 fills)
-    arena = None
-    if not frozen:
-        arena = torch.empty(_hip.STATS_REPL * 2 * sum(e.cout for e in eff.values()), dtype=torch.float64, device=dev)
-        _hip.multi([(_hip.MULTI_ZERO, arena, None)])
-    arena_used = [0]
-
-    def take(n):
-        t = arena[arena_used[0]:arena_used[0] + n]
-        arena_used[0] += n
-        return t
+    arena = StatsArena(dev, sum(e.cout for e in eff.values()), frozen)      # every layer's BN-statistics accumulators, zeroed by one launch instead of 22
     blocks = []
     written = []          # running statistics / step counters updated through raw pointers by y2_bn_finalize
 
@@ -401,8 +368,8 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
         blk.wino_v = None
         blk.eff = e
         z = _new(dev, B, h, w, cout)
-        stats = take(_hip.STATS_REPL * 2 * cout) if (blk.has_bn and not frozen) else None
-        estats = None if det else stats          # statistics accumulated by the convolution's epilogue (atomics)
+        stats = arena.take(cout) if (blk.has_bn and not frozen) else None
+        estats = arena.epilogue(stats)          # statistics accumulated by the convolution's epilogue (atomics)
         if first:
             _hip.check(L.y2_conv0_fwd(_hip.ptr(xin), _hip.ptr(e.w), None, None, _hip.ptr(z), None, _hip.ptr(estats),
                                       B, h, w, cin, cout, cout, 0, 1.0, st), 'y2_conv0_fwd')
@@ -413,26 +380,16 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
             wp = _new(dev, e.w.numel())
             _hip.check(L.y2_pack_weight(_hip.ptr(e.w), _hip.ptr(wp), cout, cin, k, 0, st), 'y2_pack_weight')
             blk.wino_v = _conv(L, st, xin, wp, z, B, h, w, cin, ldx, cout, k, cout, stats=estats, keep_v=keep_v(h, w, cin, ldx, cout, k))
-        if det and stats is not None:
-            _hip.colstats_det(z, B * h * w, cout, cout, stats)
+        arena.settle(stats, z, B * h * w, cout, cout)
         blk.z = z
-        if blk.has_bn and frozen:
-            # eval-mode BatchNorm: the folded affine of the inference path; z-hat is built from the running statistics
-            blk.scale, blk.shift = _new(dev, cout), _new(dev, cout)
-            _hip.check(L.y2_bn_fold(_hip.ptr(e.gamma), _hip.ptr(e.beta), _hip.ptr(e.rm), _hip.ptr(e.rv), BN_EPS, _hip.ptr(blk.scale), _hip.ptr(blk.shift), cout, st), 'y2_bn_fold')
-            blk.mean, blk.invstd = _hip.f32c(e.rm), torch.rsqrt(_hip.f32c(e.rv) + BN_EPS)
-        elif blk.has_bn:
+        if blk.has_bn:
             bn = mod.bn
-            blk.scale, blk.shift, blk.mean, blk.invstd = (_new(dev, cout) for _ in range(4))
-            _hip.check(L.y2_bn_finalize(_hip.ptr(stats), float(B * h * w), _hip.ptr(e.gamma), _hip.ptr(e.beta),
-                                        _hip.ptr(e.rm), _hip.ptr(e.rv), BN_MOMENTUM, BN_EPS,
-                                        _hip.ptr(blk.scale), _hip.ptr(blk.shift), _hip.ptr(blk.mean), _hip.ptr(blk.invstd), cout,
-                                        _hip.ptr(_counter(bn)), st), 'y2_bn_finalize')
-            if e.padded and bn.running_mean is not None:
+            blk.scale, blk.shift, blk.mean, blk.invstd = bn_params(L, st, dev, bn, stats, B * h * w, cout, frozen, BN_MOMENTUM, tensors=(e.gamma, e.beta, e.rm, e.rv))
+            if not frozen and e.padded and bn.running_mean is not None:          # the padded-channel variant: the kernel updated zero-padded copies
                 bn.running_mean.copy_(e.rm[:e.cout_r])
                 bn.running_var.copy_(e.rv[:e.cout_r])
                 written.extend(t for t in (bn.num_batches_tracked,) if t is not None)
-            else:
+            elif not frozen:
                 written.extend(t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None)
         else:
             blk.scale, blk.mean, blk.invstd = None, None, None
@@ -507,20 +464,8 @@ def _darknet_bwd(ctx, dout):
     B, cin0, H, W, c_pt, c_l2 = ctx.geom
     dev = dout.device
     dout = _hip.f32c(dout)
-    grads = {}
-    hook = getattr(dnn, 'grad_ready_hook', None)
-    buffer_hook = getattr(dnn, 'grad_buffer_hook', None)     # train.DataParallelRCCL: where the averaged gradient of a parameter will live (its flat-bucket slice)
-
-    def ready(param, g):
-        grads[id(param)] = g
-        if hook is not None:
-            hook(param, g)
-
-    def dest(param):
-        """Tensor a finished gradient of `param` is written to: the data-parallel bucket slice when the wrapper offers one (the
-        all-reduce then runs in place, no copy into the bucket), else fresh memory."""
-        t = buffer_hook(param) if buffer_hook is not None else None
-        return t if t is not None else _new(dev, *param.shape)
+    sink = GradSink(dnn, dev)
+    ready, dest, grads = sink.ready, sink.dest, sink.grads
 
     # gradient sources per block index: (dy_full tensor, ldf, foff, fmode), dy_pool tensor
     n = len(blocks)
@@ -557,10 +502,7 @@ def _darknet_bwd(ctx, dout):
             bufs = dnn._train_bufs = (dev, {})
 
     def persistent(tag, nel):
-        t = bufs[1].get(tag)
-        if t is None or t.numel() != nel:
-            t = bufs[1][tag] = torch.empty(nel, dtype=torch.float32, device=dev)
-        return t
+        return cached_buf(bufs[1], tag, nel, dev)
     wg = {}          # block index -> (accumulation target, it is the final gradient tensor, pre-zeroed)
     dzs = {}
     for i in order:
@@ -773,22 +715,7 @@ def _darknet_bwd(ctx, dout):
                 else:
                     src_full[prod] = (dx, cin, 0, 0)
         blk.z = None   # free as we go
-    # ---- affine-parameter gradients: fp64 sums -> fp32, one launch; straight into the data-parallel bucket slices when there are any
-    items, handed = [], []
-    gb_all = None
-    for prm, off, ln in affine_grads:
-        t = buffer_hook(prm) if buffer_hook is not None else None
-        if t is None:
-            if gb_all is None:
-                gb_all = _new(dev, sums_arena.numel())
-                items.append((_hip.MULTI_F64_TO_F32, gb_all, sums_arena))
-            t = gb_all[off:off + ln]
-        else:
-            items.append((_hip.MULTI_F64_TO_F32, t, sums_arena[off:off + ln]))
-        handed.append((prm, t))
-    _hip.multi(items, st)
-    for prm, t in handed:
-        ready(prm, t)
+    sink.hand_affine(sums_arena, affine_grads, st)          # fp64 sums -> fp32, one launch
     flush_weight_grads()
     L.y2_prof_set_tag(0)
     out = [None, grads.get('__x__')]
@@ -1063,704 +990,6 @@ def weighted_total(loss_, hparam):
     return _WeightedTotalFn.apply(vec, wd)
 
 
-# ------------------------------------------------------------------------------------------------ ResNet plugins
-class _ROp(object):
-    """One recorded operation of the ResNet training forward (conv+BN+ReLU[+residual], the stem max-pool, or a depthwise conv+BN+ReLU)."""
-    __slots__ = ('kind', 'conv', 'bn', 'x', 'ldx', 'h', 'w', 'ho', 'wo', 'stride', 'pad', 'k', 'cin', 'cout', 'z', 'scale', 'shift', 'mean', 'invstd',
-                 'residual', 'y', 'slope', 'first', 'pool', 'filt')       # pool = (ksize, stride, pad, pad_end) of a 'pool' op; filt = the filter of a 'dw' op
-
-
-def resnet_forward(net, x, frozen=False):
-    """frozen: eval()-mode BatchNorm (running statistics, nothing updated) with autograd recording."""
-    params = [p for p in net.parameters()]
-    out = ResNetTrainFn.apply(net, x, frozen, *params)
-    return out.permute(0, 3, 1, 2)
-
-
-def tiny_forward(net, x, frozen=False):
-    """Training-mode forward of model.yolo2.Tiny (model/yolo2.py:140-173) through the same op-list graph as the ResNets."""
-    params = [p for p in net.parameters()]
-    out = ResNetTrainFn.apply(net, x, frozen, *params)
-    return out.permute(0, 3, 1, 2)
-
-
-def mobilenet_forward(net, x, frozen=False):
-    """Training-mode (or frozen-BN differentiable) forward of model.mobilenet.MobileNet through the same op-list graph as the ResNets."""
-    params = [p for p in net.parameters()]
-    out = ResNetTrainFn.apply(net, x, frozen, *params)
-    return out.permute(0, 3, 1, 2)
-
-
-def densenet_forward(net, x, frozen=False):
-    """Training-mode (or frozen-BN differentiable) forward of model.densenet.DenseNet through the op-list graph of the ResNets ('pre' / 'grow' ops)."""
-    params = [p for p in net.parameters()]
-    out = ResNetTrainFn.apply(net, x, frozen, *params)
-    return out.permute(0, 3, 1, 2)
-
-
-class _DOp(object):
-    """One recorded DenseNet operation.  kind 'pre': BatchNorm -> ReLU -> 1x1 convolution [-> AvgPool 2x2] on the first K channels of a block buffer
-    (norm1 + conv1 of a dense layer with its norm2 + ReLU behind it; a transition; norm5 + the head); kind 'grow': the raw 3x3 convolution that
-    appends growth_rate channels to the block buffer."""
-    __slots__ = ('kind', 'bn', 'conv', 'buf', 'gbuf', 'K', 'ld', 'h', 'w', 'pool', 'pre_slope', 'scale', 'shift', 'mean', 'invstd', 'N', 'z', 'bn2', 'scale2',
-                 'shift2', 'mean2', 'invstd2', 'a2', 'out', 'out_ld', 'out_off', 'role')
-
-
-def _dense_conv3(L, st, x, wp, y, B, H, W, cin, cout, ldy, coff, stats):
-    """The raw 3x3 / pad 1 convolution of a dense layer writing its cout channels at channel offset coff of a block buffer."""
-    p = _hip.ConvParams()
-    p.x, p.w, p.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
-    p.stats = stats.data_ptr() if stats is not None else None
-    p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, H, W, cin, cin, cout, 3
-    p.ldy, p.coff, p.slope, p.tile = ldy, coff, 1.0, 0
-    p.stride, p.pad_plus1 = 1, 2
-    u = _hip.wino_weight(wp, cout, cin) if _hip.wino_eligible(cout, cin, 3) else None
-    _hip.autotune_conv(p, x.device, wino_w=u)
-    _hip.conv_workspace(p, x.device)
-    _hip.check(L.y2_conv_fwd(ctypes.byref(p), st), 'y2_conv_fwd')
-
-
-def _densenet_fwd(ctx, net, L, st, dev, B, H, W, x4, cpad, frozen, take_stats, prepared, conv_bn, maxpool):
-    """model/densenet.py:29-65.  A dense block is one buffer [B, h, w, C_end]; the batch statistics of a slab of it (the stem's pooled output, a
-    transition's output, the growth_rate channels of a layer) are taken ONCE, by its producer, and every consumer's BatchNorm finalises from them
-    with its own gamma / beta and updates its own running statistics (the reference recomputes the identical statistics per consumer)."""
-    import torch.nn as nn
-    f = net.features
-    for name, m in net.named_modules():
-        if isinstance(m, nn.Conv2d) and m is not f.conv and (m.weight.shape[0] % 4 or (m.weight.shape[1] % 4 and m is not f.conv0)):
-            raise RuntimeError('model.densenet: training needs widths that are multiples of 4 (%s.weight is %s)' % (name, tuple(m.weight.shape)))
-    det = _hip.ensure_deterministic(dev)
-    MOM = ResNetTrainFn.MOMENTUM
-    dops = []
-
-    def slab_stats(view, M, C, ld):
-        """deterministic mode (and the stem's pooled slab): column statistics of a finished slab"""
-        stats = take_stats(C)
-        _hip.colstats_det(view, M, C, ld, stats)
-        return stats
-
-    def finalize(bn, slabs, C, count):
-        scale, shift = _new(dev, C), _new(dev, C)
-        gamma, beta = _hip.f32c(bn.weight.detach()), _hip.f32c(bn.bias.detach())
-        if frozen:
-            _hip.check(L.y2_bn_fold(_hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(_hip.f32c(bn.running_mean)), _hip.ptr(_hip.f32c(bn.running_var)), BN_EPS,
-                                    _hip.ptr(scale), _hip.ptr(shift), C, st), 'y2_bn_fold')
-            return scale, shift, _hip.f32c(bn.running_mean), torch.rsqrt(_hip.f32c(bn.running_var) + BN_EPS)
-        mean, invstd = _new(dev, C), _new(dev, C)
-        counter = _counter(bn)
-        covered = 0
-        for off, n, stats in slabs:
-            if off >= C:
-                break
-            assert off == covered and off + n <= C
-            _hip.check(L.y2_bn_finalize(_hip.ptr(stats), float(count), _hip.ptr(gamma[off:off + n]), _hip.ptr(beta[off:off + n]),
-                                        _hip.ptr(bn.running_mean[off:off + n]), _hip.ptr(bn.running_var[off:off + n]), MOM, BN_EPS,
-                                        _hip.ptr(scale[off:off + n]), _hip.ptr(shift[off:off + n]), _hip.ptr(mean[off:off + n]), _hip.ptr(invstd[off:off + n]), n,
-                                        _hip.ptr(counter) if off == 0 else None, st), 'y2_bn_finalize')
-            covered = off + n
-        assert covered == C
-        _hip.wrote([t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None])
-        return scale, shift, mean, invstd
-
-    def pre(role, bn, conv, buf, slabs, K, ld, h, w, pool, pre_slope, out, out_ld, out_off, shift=None, want_stats=False):
-        op = _DOp()
-        op.kind, op.role, op.bn, op.conv, op.buf, op.K, op.ld, op.h, op.w, op.pool, op.pre_slope = 'pre', role, bn, conv, buf, K, ld, h, w, pool, pre_slope
-        op.scale, op.shift, op.mean, op.invstd = finalize(bn, slabs, K, B * h * w)
-        op.N = N = conv.weight.shape[0]
-        op.out, op.out_ld, op.out_off, op.bn2 = out, out_ld, out_off, None
-        stats = take_stats(N) if (want_stats and not frozen) else None
-        _hip.check(L.y2_preact_conv1x1_fwd(_hip.ptr(buf), _hip.ptr(_hip.f32c(conv.weight.detach())), _hip.ptr(op.scale), _hip.ptr(op.shift), pre_slope, None,
-                                           _hip.ptr(shift), 1.0, _hip.ptr(out), None if det else _hip.ptr(stats), B, h, w, K, ld, N, out_ld, out_off, pool, st),
-                   'y2_preact_conv1x1_fwd')
-        ho, wo = (h // 2, w // 2) if pool else (h, w)
-        if det and stats is not None:
-            _hip.colstats_det(out.view(-1)[out_off:], B * ho * wo, N, out_ld, stats)
-        dops.append(op)
-        return op, stats
-
-    # ---- stem: conv0 + norm0 + ReLU + MaxPool2d(3, 2, 1) (the ResNet stem ops), copied into block buffer 1
-    c0 = f.conv0.weight.shape[0]
-    cur, h, w, _ = conv_bn(f.conv0, f.norm0, x4, cpad, H, W, 2, 3, 0.0, first=True)
-    pooled, h, w = maxpool(cur, h, w, c0, 3, 2, 1, 1)
-    c, buf, prev = c0, None, None
-    blocks = net.blocks()
-    for bi, (block, trans) in enumerate(blocks):
-        c_end = c + sum(layer.conv2.weight.shape[0] for layer in block)
-        nxt = _new(dev, B, h, w, c_end)
-        if bi == 0:
-            _hip.check(L.y2_bn_act_fwd(_hip.ptr(pooled), None, None, 1.0, _hip.ptr(nxt), None, B, h, w, c0, c0, c_end, 0, 0, 0, 0, st), 'y2_bn_act_fwd')
-            slabs = [(0, c0, None if frozen else slab_stats(pooled, B * h * w, c0, c0))]
-        else:
-            pbuf, pslabs, pc, ph, pw, ptr_ = prev
-            op, stats = pre('trans', ptr_.norm, ptr_.conv, pbuf, pslabs, pc, pc, ph, pw, 1, 0.0, nxt, c_end, 0, want_stats=True)
-            slabs = [(0, c, stats)]
-        buf = nxt
-        for layer in block:
-            n1, g = layer.conv1.weight.shape[0], layer.conv2.weight.shape[0]
-            z1 = _new(dev, B, h, w, n1)
-            op, stats1 = pre('layer', layer.norm1, layer.conv1, buf, slabs, c, c_end, h, w, 0, 0.0, z1, n1, 0, want_stats=True)
-            op.z, op.bn2 = z1, layer.norm2
-            op.scale2, op.shift2, op.mean2, op.invstd2 = finalize(layer.norm2, [(0, n1, stats1)], n1, B * h * w)
-            a2 = _new(dev, B, h, w, n1)
-            _hip.check(L.y2_bn_act_fwd_ex(_hip.ptr(z1), _hip.ptr(op.scale2), _hip.ptr(op.shift2), 0.0, None, 0, _hip.ptr(a2), None, B, h, w, n1, n1, n1, 0, 0, 0, 0, st),
-                       'y2_bn_act_fwd_ex')
-            op.a2 = a2
-            wp = prepared[layer.conv2]['wp']
-            gstats = take_stats(g) if not frozen else None
-            _dense_conv3(L, st, a2, wp, buf, B, h, w, n1, g, c_end, c, None if det else gstats)
-            if det and gstats is not None:
-                _hip.colstats_det(buf.view(-1)[c:], B * h * w, g, c_end, gstats)
-            grow = _DOp()
-            grow.kind, grow.conv, grow.buf, grow.K, grow.ld, grow.h, grow.w, grow.N, grow.a2, grow.out_off = 'grow', layer.conv2, buf, n1, c_end, h, w, g, a2, c
-            dops.append(grow)
-            slabs.append((c, g, gstats))
-            c += g
-        if trans is not None:
-            prev = (buf, slabs, c_end, h, w, trans)
-            c = trans.conv.weight.shape[0]
-            h, w = h // 2, w // 2
-    nout = f.conv.weight.shape[0]
-    out = _new(dev, B, h, w, nout)
-    op, _ = pre('head', f.norm5, f.conv, buf, slabs, c, c, h, w, 0, 1.0, out, nout, 0, shift=_hip.f32c(f.conv.bias.detach()))
-    op.z = out
-    ctx.dense = dict(ops=dops, pooled=pooled, c0=c0)
-    return out
-
-
-def _densenet_bwd(ctx, dout, ready, dest, buffer_hook):
-    """Reverse walk of the 'pre' / 'grow' ops.  Every block has ONE gradient buffer [B, h, w, C_end]: the block's consumer (transition / head) writes
-    all of it through y2_preact_bwd, every layer then reads the finished gradient of its own slab and ADDS its input gradient into the first K
-    channels.  Returns the gradient of the stem's pooled output (the ResNet stem ops finish the walk)."""
-    L, st = _hip.lib(), _hip.stream()
-    dense, B, net = ctx.dense, ctx.B, ctx.net
-    dev = dout.device
-    prepared = ctx.prepared
-    dops = dense['ops']
-    pres = [op for op in dops if op.kind == 'pre']
-    total = sum(2 * op.K + (2 * op.N if op.bn2 is not None else 0) for op in pres)
-    nout = pres[-1].N
-    sums_arena = torch.empty(total + 2 * nout, dtype=torch.float64, device=dev)
-    head = pres[-1]
-    head_cop = (nout + 3) // 4 * 4
-    head_dz = _new(dev, B, head.h, head.w, head_cop)
-    head_dwp, head_w = _new(dev, head_cop * head.K), _new(dev, head_cop, head.K, 1, 1)
-    zero = [sums_arena, head_dz, head_dwp, head_w]
-    wbuf = {}
-    for op in pres:          # the 1x1 weight gradients: [N][1][K] IS the state_dict layout; the direct kernel adds split partial sums into a zeroed buffer
-        if op.role != 'head':
-            wbuf[id(op)] = dest(op.conv.weight)
-            zero.append(wbuf[id(op)].view(-1))
-    for i in range(0, len(zero), 64):          # (Y2_MULTI_MAX_ITEMS entries per launch)
-        _hip.multi([(_hip.MULTI_ZERO, t, None) for t in zero[i:i + 64]], st)
-    has_bn = 2 if ctx.frozen else 1
-    affine, off = [], 0
-    gbufs = {}
-
-    def gbuf_of(op):
-        t = gbufs.get(id(op.buf))
-        if t is None:
-            t = gbufs[id(op.buf)] = _new(dev, *op.buf.shape)
-        return t
-
-    def dgrad(conv, dz, h, w, cop, ldz, cin, k, wd=None):
-        if wd is None:
-            wd = prepared[conv]['wd']
-        dx = _new(dev, B, h, w, cin)
-        _gen_conv(L, st, dz, wd, dx, B, h, w, cop, ldz, cin, k, 1, k - 1 - (k - 1) // 2)
-        return dx
-
-    def bn_sums(bn, C):
-        nonlocal off
-        t = sums_arena[off:off + 2 * C]
-        affine.append((bn.bias, off, C))
-        affine.append((bn.weight, off + C, C))
-        off += 2 * C
-        return t
-
-    for op in reversed(dops):
-        h, w = op.h, op.w
-        if op.kind == 'grow':
-            # 3x3: weight gradient from (a2, gradient of the slab), data gradient -> gradient of a2 (kept on the op for the 'pre' op in front of it)
-            gb = gbuf_of(op)
-            dslab = gb.view(-1)[op.out_off:]
-            n1, g = op.K, op.N
-            dwp = _hip.conv_wgrad(op.a2, dslab, B, h, w, n1, n1, g, op.ld, 3)
-            dw = dest(op.conv.weight)
-            _hip.check(L.y2_unpack_weight_grad(_hip.ptr(dwp), _hip.ptr(dw), g, n1, 3, st), 'y2_unpack_weight_grad')
-            ready(op.conv.weight, dw)
-            op.z = dgrad(op.conv, dslab, h, w, g, op.ld, n1, 3)
-            grow = op
-            continue
-        ho, wo = (h // 2, w // 2) if op.pool else (h, w)
-        K, N = op.K, op.N
-        if op.role == 'head':
-            # bias + no activation (has_bn = 0: dz = dout, sums = d bias), written zero-padded to a multiple of 4 channels for the GEMM kernels
-            cop, dz, dwp, wsrc = head_cop, head_dz, head_dwp, head_w
-            bsum = sums_arena[total:total + 2 * N]
-            _hip.check(L.y2_bn_act_bwd_ex(_hip.ptr(op.z), None, _hip.ptr(_hip.f32c(op.conv.bias.detach())), None, None, None, 1.0, _hip.ptr(_hip.f32c(dout)), N, 0, 0,
-                                          None, 0, 0, None, 0, None, 0, None, 0, _hip.ptr(bsum), _hip.ptr(dz), cop, B, ho, wo, N, N, 0, st), 'y2_bn_act_bwd_ex')
-            affine.append((op.conv.bias, total, N))
-            ldz = cop
-            wsrc[:N] = _hip.f32c(op.conv.weight.detach())
-            wd = _new(dev, wsrc.numel())
-            _hip.check(L.y2_pack_weight(_hip.ptr(wsrc), _hip.ptr(wd), cop, K, 1, 1, st), 'y2_pack_weight')
-        elif op.role == 'trans':
-            cop, wd = N, None
-            nb = [o for o in dops if o.kind == 'pre' and o.buf is op.out][0]
-            dz = gbuf_of(nb)          # the first N channels of the next block's gradient buffer
-            ldz = op.out_ld
-            dwp = wbuf[id(op)].view(-1)
-        else:
-            # norm2 + ReLU between the 1x1 and the 3x3: gradient of a2 (from the 'grow' op) -> gradient of the raw 1x1 output
-            cop, wd, ldz = N, None, N
-            dz = _new(dev, B, h, w, N)
-            _hip.check(L.y2_bn_act_bwd_ex(_hip.ptr(op.z), _hip.ptr(op.scale2), _hip.ptr(op.shift2), _hip.ptr(op.mean2), _hip.ptr(op.invstd2),
-                                          _hip.ptr(op.bn2.weight.detach()), 0.0, _hip.ptr(grow.z), N, 0, 0, None, 0, 0, None, 0, None, 0, None, 0,
-                                          _hip.ptr(bn_sums(op.bn2, N)), _hip.ptr(dz), N, B, h, w, N, N, has_bn, st), 'y2_bn_act_bwd_ex')
-            grow.z = None
-            dwp = wbuf[id(op)].view(-1)
-        # 1x1 weight gradient from the recomputed pre-activated operand
-        act = _new(dev, B, ho, wo, K)
-        _hip.check(L.y2_preact_fwd(_hip.ptr(op.buf), _hip.ptr(op.scale), _hip.ptr(op.shift), op.pre_slope, _hip.ptr(act), B, h, w, K, op.ld, K, op.pool, st), 'y2_preact_fwd')
-        _hip.check(L.y2_conv_wgrad_ex(_hip.ptr(act), _hip.ptr(dz), _hip.ptr(dwp), B, ho, wo, K, K, cop, ldz, 1, 1, 0, st), 'y2_conv_wgrad_ex')
-        if op.role == 'head':
-            ready(op.conv.weight, dwp.view(cop, K, 1, 1)[:N].contiguous())
-        else:
-            ready(op.conv.weight, wbuf[id(op)])
-        dA = dgrad(op.conv, dz, ho, wo, cop, ldz, K, 1, wd=wd)
-        _hip.check(L.y2_preact_bwd(_hip.ptr(op.buf), _hip.ptr(op.scale), _hip.ptr(op.shift), op.pre_slope, _hip.ptr(op.mean), _hip.ptr(op.invstd),
-                                   _hip.ptr(op.bn.weight.detach()), _hip.ptr(dA), K, _hip.ptr(bn_sums(op.bn, K)), _hip.ptr(gbuf_of(op)), op.ld,
-                                   1 if op.role == 'layer' else 0, B, h, w, K, op.ld, op.pool, has_bn, st), 'y2_preact_bwd')
-        op.z = op.a2 = None
-    # ---- affine-parameter gradients: fp64 sums -> fp32, one launch
-    items, handed, gb_all = [], [], None
-    for prm, o, ln in affine:
-        t = buffer_hook(prm) if buffer_hook is not None else None
-        if t is None:
-            if gb_all is None:
-                gb_all = _new(dev, sums_arena.numel())
-                items.append((_hip.MULTI_F64_TO_F32, gb_all, sums_arena))
-            t = gb_all[o:o + ln]
-        else:
-            items.append((_hip.MULTI_F64_TO_F32, t, sums_arena[o:o + ln]))
-        handed.append((prm, t))
-    for i in range(0, len(items), 64):
-        _hip.multi(items[i:i + 64], st)
-    for prm, t in handed:
-        ready(prm, t)
-    # ---- gradient of the stem's pooled output: the first c0 channels of block 1's gradient buffer
-    first = dops[0]
-    c0 = dense['c0']
-    dpool = _new(dev, *dense['pooled'].shape)
-    gb = gbufs[id(first.buf)]
-    _hip.check(L.y2_bn_act_fwd(_hip.ptr(gb), None, None, 1.0, _hip.ptr(dpool), None, B, first.h, first.w, c0, first.ld, c0, 0, 0, 0, 0, st), 'y2_bn_act_fwd')
-    ctx.dense = None
-    return dpool
-
-
-def _gen_conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, stride, pad, stats=None, transposed=False, out_hw=None):
-    p = _hip.ConvParams()
-    p.x, p.w, p.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
-    p.stats = stats.data_ptr() if stats is not None else None
-    p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, H, W, cin, ldx, cout, k
-    p.ldy, p.slope, p.tile = cout, 1.0, 0
-    p.stride, p.pad_plus1 = stride, pad + 1
-    if transposed:
-        p.transposed, p.out_h, p.out_w = 1, out_hw[0], out_hw[1]
-    u = _hip.wino_weight(wp, cout, cin) if (not transposed and stride == 1 and pad == 1 and _hip.wino_eligible(cout, cin, k)) else None
-    _hip.autotune_conv(p, x.device, wino_w=u)
-    _hip.conv_workspace(p, x.device)
-    _hip.check(L.y2_conv_fwd(ctypes.byref(p), st), 'y2_conv_fwd')
-
-
-def _resnet_operands(net, dev, scope=None):
-    """{nn.Conv2d: dict(wp, wd)}: the forward / data-gradient GEMM operands of every convolution of a ResNet / Tiny plugin whose channel
-    counts need no padding, derived by ONE y2_prep_weights launch per parameter version (the per-layer path costs two y2_pack_weight
-    launches per convolution and step: 107 for ResNet-50).  scope: see _train_operands."""
-    import torch.nn as nn
-    convs = [m for m in net.modules() if isinstance(m, nn.Conv2d)]
-    key = (dev, tuple((c.weight.data_ptr(), c.weight._version) for c in convs))
-    if scope is not None:
-        bufs = scope
-    else:
-        cache = net.__dict__.get('_train_cache')
-        if cache is not None and cache[0] == key:
-            return cache[1]
-        held = net.__dict__.get('_train_bufs')
-        if held is None or held[0] != dev:
-            held = net.__dict__['_train_bufs'] = (dev, {})
-        bufs = held[1]
-    items, ops = [], {}
-    for i, c in enumerate(convs):
-        w = c.weight.detach()
-        cout, cin, k, _ = w.shape
-        if cout % 4 or cin % 4 or not w.is_contiguous() or w.dtype != torch.float32 or not w.is_cuda:
-            continue          # the 3-channel stem and the 425-wide head run zero-padded: per-layer path
-        d = {}
-        for tag, mode in (('wp', _hip.PREP_FPROP), ('wd', _hip.PREP_DGRAD)):
-            t = bufs.get(('rn', i, tag))
-            if t is None or t.numel() != w.numel():
-                t = bufs[('rn', i, tag)] = torch.empty(w.numel(), dtype=torch.float32, device=dev)
-            d[tag] = t
-            items.append((w, t, cout, cin, k, mode))
-        ops[c] = d
-    if items:
-        table = (_hip.PrepItem * len(items))()
-        for e, (src, dst, cout, cin, k, mode) in zip(table, items):
-            e.src, e.dst, e.Cout, e.Cin, e.ksize, e.mode = src.data_ptr(), dst.data_ptr(), cout, cin, k, mode
-        _hip.check(_hip.lib().y2_prep_weights(table, len(items), _hip.stream()), 'y2_prep_weights')
-    if scope is None:
-        net.__dict__['_train_cache'] = (key, ops)
-    return ops
-
-
-class ResNetTrainFn(torch.autograd.Function):
-    """Training graph of model.resnet.ResNet (model/resnet.py:29-158): per convolution {raw general conv with BN statistics in the
-    epilogue -> y2_bn_finalize (momentum 0.1) -> y2_bn_act_fwd_ex (affine [+ residual] + ReLU)}; backward in reverse with
-    gradient fan-in per tensor: y2_bn_act_bwd_ex (ReLU mask from the recomputed pre-activation, BN backward, gradient of
-    the residual input) -> y2_conv_wgrad_ex -> data gradient (stride 1: forward kernel on rotated weights; stride 2:
-    transposed mode of the general kernel); the stem max-pool goes through y2_maxpool_fwd / y2_maxpool_bwd.
-    Also the graph of model.yolo2.Tiny and of model.mobilenet.MobileNet, whose depthwise convolutions are 'dw' ops: y2_dwconv_fwd
-    (raw, BN statistics) -> y2_bn_finalize -> y2_bn_act_fwd_ex; backward y2_bn_act_bwd_ex -> y2_dwconv_wgrad -> y2_dwconv_dgrad."""
-    MOMENTUM = 0.1
-
-    @staticmethod
-    def forward(ctx, net, x, frozen, *params):
-        _hip.require_gpu(x)
-        ctx.need_dx = x.requires_grad
-        L = _hip.lib()
-        st = _hip.stream()
-        x = _hip.f32c(x.detach())
-        B, cin0, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError('input size must be a multiple of 32 (got %dx%d)' % (H, W))
-        dev = x.device
-        ops = []
-        ctx.frozen = frozen
-        scope = getattr(ctx, 'scope', None)
-        prepared = ctx.prepared = _resnet_operands(net, dev, scope)
-        ctx.prepared_key = net.__dict__['_train_cache'][0] if scope is None else None
-        import torch.nn as nn
-        # one zero-filled arena for the replicated BatchNorm-statistics accumulators of every convolution (one launch instead of 53 fills)
-        arena = None
-        if not frozen:
-            arena = torch.empty(_hip.STATS_REPL * 2 * sum(m.num_features for m in net.modules() if isinstance(m, nn.BatchNorm2d)), dtype=torch.float64, device=dev)
-            if arena.numel():
-                _hip.multi([(_hip.MULTI_ZERO, arena, None)])
-        used = [0]
-        cpad = (cin0 + 3) // 4 * 4
-        x4 = _new(dev, B, H, W, cpad)
-        _hip.check(L.y2_nchw_to_nhwc(_hip.ptr(x), _hip.ptr(x4), B, cin0, H, W, cpad, st), 'y2_nchw_to_nhwc')
-        ctx.x4, ctx.cin0 = x4, cin0
-
-        def conv_bn(conv, bn, xin, ldx, h, w, stride, pad, slope, residual=None, first=False, momentum=None):
-            op = _ROp()
-            weight = _hip.f32c(conv.weight.detach())
-            cout, cin_true, k, _ = weight.shape
-            if ldx % 4 or (cin_true % 4 and not first):
-                raise RuntimeError('training needs conv input channel counts that are multiples of 4 (got %d)' % cin_true)
-            if cin_true != ldx:           # stem: zero-padded input channels
-                wpad = torch.zeros(cout, ldx, k, k, dtype=torch.float32, device=dev)
-                wpad[:, :cin_true] = weight
-                weight = wpad
-            if conv in prepared and cin_true == ldx:
-                wp = prepared[conv]['wp']
-            else:
-                wp = _new(dev, weight.numel())
-                _hip.check(L.y2_pack_weight(_hip.ptr(weight), _hip.ptr(wp), cout, ldx, k, 0, st), 'y2_pack_weight')
-            ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-            z = _new(dev, B, ho, wo, cout)
-            stats = None
-            if bn is not None and not frozen:
-                stats = arena[used[0]:used[0] + _hip.STATS_REPL * 2 * cout]
-                used[0] += _hip.STATS_REPL * 2 * cout
-            det = _hip.ensure_deterministic(dev)
-            _gen_conv(L, st, xin, wp, z, B, h, w, ldx, ldx, cout, k, stride, pad, stats=None if det else stats)
-            if det and stats is not None:
-                _hip.colstats_det(z, B * ho * wo, cout, cout, stats)
-            op.kind, op.conv, op.bn, op.x, op.ldx, op.h, op.w, op.ho, op.wo = 'conv', conv, bn, xin, ldx, h, w, ho, wo
-            op.stride, op.pad, op.k, op.cin, op.cout, op.z, op.residual, op.slope, op.first = stride, pad, k, cin_true, cout, z, residual, slope, first
-            return bn_act(op, conv, bn, stats, cout, ho, wo, slope, residual, momentum)
-
-        def bn_act(op, conv, bn, stats, cout, ho, wo, slope, residual, momentum):
-            if bn is not None and frozen:
-                op.scale, op.shift = _new(dev, cout), _new(dev, cout)
-                _hip.check(L.y2_bn_fold(_hip.ptr(_hip.f32c(bn.weight.detach())), _hip.ptr(_hip.f32c(bn.bias.detach())), _hip.ptr(_hip.f32c(bn.running_mean)),
-                                        _hip.ptr(_hip.f32c(bn.running_var)), BN_EPS, _hip.ptr(op.scale), _hip.ptr(op.shift), cout, st), 'y2_bn_fold')
-                op.mean, op.invstd = _hip.f32c(bn.running_mean), torch.rsqrt(_hip.f32c(bn.running_var) + BN_EPS)
-            elif bn is not None:
-                op.scale, op.shift, op.mean, op.invstd = (_new(dev, cout) for _ in range(4))
-                _hip.check(L.y2_bn_finalize(_hip.ptr(stats), float(B * ho * wo), _hip.ptr(bn.weight.detach()), _hip.ptr(bn.bias.detach()),
-                                            _hip.ptr(bn.running_mean), _hip.ptr(bn.running_var), ResNetTrainFn.MOMENTUM if momentum is None else momentum, BN_EPS,
-                                            _hip.ptr(op.scale), _hip.ptr(op.shift), _hip.ptr(op.mean), _hip.ptr(op.invstd), cout,
-                                            _hip.ptr(_counter(bn)), st), 'y2_bn_finalize')
-                _hip.wrote([t for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None])      # written through raw pointers
-            else:
-                op.scale = op.mean = op.invstd = None
-                op.shift = _hip.f32c(conv.bias.detach()) if conv.bias is not None else None
-            y = _new(dev, B, ho, wo, cout)
-            _hip.check(L.y2_bn_act_fwd_ex(_hip.ptr(op.z), _hip.ptr(op.scale), _hip.ptr(op.shift), slope, _hip.ptr(residual), cout if residual is not None else 0,
-                                          _hip.ptr(y), None, B, ho, wo, cout, cout, cout, 0, 0, 0, 0, st), 'y2_bn_act_fwd_ex')
-            op.y = y
-            ops.append(op)
-            return y, ho, wo, cout
-
-        def dwconv_bn(conv, bn, xin, C, h, w, stride):
-            # depthwise 3x3 / pad 1 (model/mobilenet.py conv_dw): raw output with the BN statistics, then the shared BN + ReLU step
-            op = _ROp()
-            weight = _hip.f32c(conv.weight.detach())
-            ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-            z = _new(dev, B, ho, wo, C)
-            stats = None
-            if not frozen:
-                stats = arena[used[0]:used[0] + _hip.STATS_REPL * 2 * C]
-                used[0] += _hip.STATS_REPL * 2 * C
-            det = _hip.ensure_deterministic(dev)
-            _hip.check(L.y2_dwconv_fwd(_hip.ptr(xin), _hip.ptr(weight), None, None, 1.0, _hip.ptr(z), None if (det or stats is None) else _hip.ptr(stats),
-                                       B, h, w, C, C, C, stride, st), 'y2_dwconv_fwd')
-            if det and stats is not None:
-                _hip.colstats_det(z, B * ho * wo, C, C, stats)
-            op.kind, op.conv, op.bn, op.x, op.ldx, op.h, op.w, op.ho, op.wo = 'dw', conv, bn, xin, C, h, w, ho, wo
-            op.stride, op.pad, op.k, op.cin, op.cout, op.z, op.residual, op.slope, op.first = stride, 1, 3, C, C, z, None, 0.0, False
-            op.filt = weight           # the data gradient reads the filter the forward read
-            y, ho, wo, _ = bn_act(op, conv, bn, stats, C, ho, wo, 0.0, None, None)
-            return y, ho, wo
-
-        def maxpool(cur, h, w, ld, ksize, stride, pad, pad_end):
-            pool = _ROp()
-            pool.kind, pool.x, pool.h, pool.w, pool.cout, pool.pool = 'pool', cur, h, w, ld, (ksize, stride, pad, pad_end)
-            ph, pw = (h + pad + pad_end - ksize) // stride + 1, (w + pad + pad_end - ksize) // stride + 1
-            pooled = _new(dev, B, ph, pw, ld)
-            _hip.check(L.y2_maxpool_fwd(_hip.ptr(cur), _hip.ptr(pooled), B, h, w, ld, ld, ld, ksize, stride, pad, pad_end, st), 'y2_maxpool_fwd')
-            pool.y, pool.ho, pool.wo = pooled, ph, pw
-            ops.append(pool)
-            return pooled, ph, pw
-
-        from model import yolo2 as _yolo2
-        if isinstance(net, _yolo2.Tiny):
-            # model/yolo2.py:140-173: nn.Sequential of Conv2d blocks (BN momentum 0.01, LeakyReLU 0.1), MaxPool2d(2) and the
-            # ConstantPad2d((0,1,0,1)) + MaxPool2d(2, stride=1) pair; the 3-channel input runs zero-padded to 4 NHWC channels
-            cur, h, w, ld = x4, H, W, cpad
-            mods = list(net.layers)
-            i = 0
-            while i < len(mods):
-                m = mods[i]
-                if isinstance(m, _yolo2.Conv2d):
-                    cur, h, w, ld = conv_bn(m.conv, m.bn, cur, ld, h, w, 1, (m.kernel_size - 1) // 2, LEAKY if m.has_act else 1.0,
-                                            first=(i == 0), momentum=BN_MOMENTUM)
-                elif isinstance(m, _yolo2._PadPool):
-                    cur, h, w = maxpool(cur, h, w, ld, 2, 1, 0, 1)
-                    i += 1          # the pad + pool pair
-                else:
-                    cur, h, w = maxpool(cur, h, w, ld, 2, 2, 0, 0)
-                i += 1
-            ctx.net, ctx.ops, ctx.B = net, ops, B
-            ctx.param_ids = [id(p) for p in params]
-            return cur
-        from model import mobilenet as _mobilenet
-        if isinstance(net, _mobilenet.MobileNet):
-            # model/mobilenet.py:54-85: 3x3/s2 stem, 13 units of {depthwise 3x3 + BN + ReLU, pointwise 1x1 + BN + ReLU}, 1x1 head with bias
-            for name, conv in [('layers.0.conv', net.stem().conv)] + [('%s.pw.conv' % n, u.pw.conv) for n, u, _ in net.units()]:
-                if conv.weight.shape[0] % 4:
-                    raise RuntimeError('model.mobilenet: training needs widths that are multiples of 4 (%s.weight has %d output channels)'
-                                       % (name, conv.weight.shape[0]))
-            stem = net.stem()
-            cur, h, w, ld = conv_bn(stem.conv, stem.bn, x4, cpad, H, W, 2, 1, 0.0, first=True)
-            for _, unit, s in net.units():
-                cur, h, w = dwconv_bn(unit.dw.conv, unit.dw.bn, cur, ld, h, w, s)
-                cur, h, w, ld = conv_bn(unit.pw.conv, unit.pw.bn, cur, ld, h, w, 1, 0, 0.0)
-            cur, _, _, _ = conv_bn(net.head(), None, cur, ld, h, w, 1, 0, 1.0)
-            ctx.net, ctx.ops, ctx.B = net, ops, B
-            ctx.param_ids = [id(p) for p in params]
-            return cur
-        from model import densenet as _densenet
-        ctx.dense = None
-        if isinstance(net, _densenet.DenseNet):
-            def take_stats(C):
-                t = arena[used[0]:used[0] + _hip.STATS_REPL * 2 * C]
-                used[0] += _hip.STATS_REPL * 2 * C
-                return t
-            out = _densenet_fwd(ctx, net, L, st, dev, B, H, W, x4, cpad, frozen, take_stats, prepared, conv_bn, maxpool)
-            ctx.net, ctx.ops, ctx.B = net, ops, B
-            ctx.param_ids = [id(p) for p in params]
-            return out
-        cur, h, w, ld = conv_bn(net.conv1, net.bn1, x4, cpad, H, W, 2, 3, 0.0, first=True)
-        cur, h, w = maxpool(cur, h, w, ld, 3, 2, 1, 1)
-        for layer in (net.layer1, net.layer2, net.layer3, net.layer4):
-            for blk in layer:
-                residual = cur
-                if blk.downsample is not None:
-                    residual, _, _, _ = conv_bn(blk.downsample[0], blk.downsample[1], cur, ld, h, w, blk.stride, 0, 1.0)
-                t, th, tw, tld = cur, h, w, ld
-                convs = blk.convs()
-                for i, (conv, bn, cs, cp) in enumerate(convs):
-                    last = i == len(convs) - 1
-                    t, th, tw, tld = conv_bn(conv, bn, t, tld, th, tw, cs, cp, 0.0, residual=residual if last else None)
-                cur, h, w, ld = t, th, tw, tld
-        out, _, _, _ = conv_bn(net.conv, None, cur, ld, h, w, 1, 0, 1.0)
-        ctx.net, ctx.ops, ctx.B = net, ops, B
-        ctx.param_ids = [id(p) for p in params]
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        L = _hip.lib()
-        st = _hip.stream()
-        net, ops, B = ctx.net, ctx.ops, ctx.B
-        dev = dout.device
-        prepared = getattr(ctx, 'prepared', None) or {}
-        if prepared and getattr(ctx, 'prepared_key', None) is not None and net.__dict__.get('_train_cache', (None,))[0] != ctx.prepared_key:
-            raise RuntimeError('model.resnet: a convolution weight was modified between this forward and its backward; the per-model GEMM operand '
-                               'buffers this graph was recorded against hold other weights now')
-        grads = {}
-        hook = getattr(net, 'grad_ready_hook', None)
-        buffer_hook = getattr(net, 'grad_buffer_hook', None)
-
-        def ready(param, g):
-            grads[id(param)] = g
-            if hook is not None:
-                hook(param, g)
-
-        def dest(param):
-            t = buffer_hook(param) if buffer_hook is not None else None
-            return t if t is not None else _new(dev, *param.shape)
-        if getattr(ctx, 'dense', None) is not None:
-            dout = _densenet_bwd(ctx, dout, ready, dest, buffer_hook)          # leaves the stem ops (conv0 + norm0 + ReLU, max-pool) to the walk below
-        convs = [op for op in ops if op.kind in ('conv', 'dw')]
-        # everything that must start from zero, filled by ONE launch: the fp64 sums of every BatchNorm backward, the accumulation targets of the
-        # direct (split, atomically added) weight gradients, the zero-padded gradient of the 425-wide head
-        sums_arena = torch.empty(2 * sum(op.cout for op in convs), dtype=torch.float64, device=dev)
-        zero = [sums_arena]
-        plan = {}
-        off = 0
-        for op in convs:
-            cout, cin, k = op.cout, op.ldx, op.k
-            cop = (cout + 3) // 4 * 4
-            e = plan[id(op)] = dict(sums=sums_arena[off:off + 2 * cout], off=off)
-            off += 2 * cout
-            e['dz'] = None
-            if op.kind == 'dw':
-                e['wino'] = False
-                continue
-            if cop != cout:
-                e['dz'] = _new(dev, B, op.ho, op.wo, cop)
-                zero.append(e['dz'])
-            wino = k == 3 and op.stride == 1 and op.pad == 1
-            e['wino'] = wino
-            if not wino:
-                # [cop][k*k][cin]: for a 1x1 convolution that IS the state_dict layout - the kernel writes the gradient tensor itself
-                direct_out = k == 1 and cop == cout and cin == op.cin
-                e['dwp'] = dest(op.conv.weight).view(-1) if direct_out else _new(dev, cop * k * k * cin)
-                e['final'] = direct_out
-                zero.append(e['dwp'])
-        _hip.multi([(_hip.MULTI_ZERO, t, None) for t in zero], st)
-        affine = []
-        G = {id(ops[-1].y): [_hip.f32c(dout)]}      # gradient sources per activation tensor
-        for op in reversed(ops):
-            srcs = G.pop(id(op.y), [])
-            assert 1 <= len(srcs) <= 2, len(srcs)
-            if op.kind == 'pool':
-                dx = _new(dev, B, op.h, op.w, op.cout)
-                pk, ps, pp, pe = op.pool
-                _hip.check(L.y2_maxpool_bwd(_hip.ptr(op.x), _hip.ptr(srcs[0]), _hip.ptr(srcs[1]) if len(srcs) > 1 else None, _hip.ptr(dx),
-                                            B, op.h, op.w, op.cout, op.cout, op.cout, op.cout, pk, ps, pp, pe, st), 'y2_maxpool_bwd')
-                G.setdefault(id(op.x), []).append(dx)
-                continue
-            cout, cin, k, ho, wo = op.cout, op.ldx, op.k, op.ho, op.wo
-            cop = (cout + 3) // 4 * 4
-            e = plan[id(op)]
-            sums, dz = e['sums'], (e['dz'] if e['dz'] is not None else _new(dev, B, ho, wo, cop))
-            dres = _new(dev, B, ho, wo, cout) if op.residual is not None else None
-            has_bn = op.bn is not None
-            _hip.check(L.y2_bn_act_bwd_ex(_hip.ptr(op.z), _hip.ptr(op.scale), _hip.ptr(op.shift), _hip.ptr(op.mean), _hip.ptr(op.invstd),
-                                          _hip.ptr(op.bn.weight.detach()) if has_bn else None, op.slope,
-                                          _hip.ptr(srcs[0]), cout, 0, 0, None, 0, 0,
-                                          _hip.ptr(srcs[1]) if len(srcs) > 1 else None, cout,
-                                          _hip.ptr(op.residual), cout if op.residual is not None else 0, _hip.ptr(dres), cout,
-                                          _hip.ptr(sums), _hip.ptr(dz), cop, B, ho, wo, cout, cout, (2 if ctx.frozen else 1) if has_bn else 0, st), 'y2_bn_act_bwd_ex')
-            if op.residual is not None:
-                G.setdefault(id(op.residual), []).append(dres)
-            # parameter gradients of the affine part = the fp64 sums of pass 1: converted for ALL layers by one launch after the loop
-            if has_bn:
-                affine.append((op.bn.bias, e['off'], cout))
-                affine.append((op.bn.weight, e['off'] + cout, cout))
-            elif op.conv.bias is not None:
-                affine.append((op.conv.bias, e['off'], cout))
-            if op.kind == 'dw':
-                # ---- depthwise: weight gradient straight into the state_dict layout (two fixed-order stages), data gradient in gather form
-                C = op.cout
-                dw = dest(op.conv.weight)
-                nws = L.y2_dwconv_wgrad_workspace_bytes(B, op.h, op.w, C, op.stride)
-                ws = _new(dev, max(nws // 4, 4))
-                _hip.check(L.y2_dwconv_wgrad(_hip.ptr(op.x), _hip.ptr(dz), _hip.ptr(dw), _hip.ptr(ws), ws.numel() * 4, B, op.h, op.w, C, C, C, op.stride, st),
-                           'y2_dwconv_wgrad')
-                ready(op.conv.weight, dw)
-                op.z = None
-                dx = _new(dev, B, op.h, op.w, C)
-                _hip.check(L.y2_dwconv_dgrad(_hip.ptr(dz), _hip.ptr(op.filt), _hip.ptr(dx), B, op.h, op.w, C, C, C, op.stride, st), 'y2_dwconv_dgrad')
-                G.setdefault(id(op.x), []).append(dx)
-                continue
-            # ---- weight gradient
-            if e['wino']:
-                dwp = _hip.conv_wgrad(op.x, dz, B, op.h, op.w, cin, cin, cop, cop, k)     # direct or Winograd, by measurement
-            else:
-                dwp = e['dwp']
-                _hip.check(L.y2_conv_wgrad_ex(_hip.ptr(op.x), _hip.ptr(dz), _hip.ptr(dwp), B, op.h, op.w, cin, cin, cop, cop, k, op.stride, op.pad, st), 'y2_conv_wgrad_ex')
-            if not e['wino'] and e['final']:
-                ready(op.conv.weight, dwp.view(cout, cin, 1, 1))
-            else:
-                dw = dest(op.conv.weight) if (cop == cout and cin == op.cin) else _new(dev, cop, cin, k, k)
-                _hip.check(L.y2_unpack_weight_grad(_hip.ptr(dwp), _hip.ptr(dw), cop, cin, k, st), 'y2_unpack_weight_grad')
-                ready(op.conv.weight, dw if (cop == cout and cin == op.cin) else dw[:cout, :op.cin].contiguous())
-            op.z = None
-            if op.first and not ctx.need_dx:
-                continue
-            # ---- data gradient (of the first layer only when the image's gradient is wanted: its result is the 4-channel NHWC image gradient)
-            ready_ops = prepared.get(op.conv)
-            if ready_ops is not None and cop == cout and op.cin == cin:
-                wd = ready_ops['wd']          # rotated / in-out-swapped operand prepared with the forward's (same parameter version)
-            else:
-                wsrc = _hip.f32c(op.conv.weight.detach())
-                if cop != cout or wsrc.shape[1] != cin:          # zero rows for padded output channels, zero columns for the stem's padded input channels
-                    wpad = torch.zeros(cop, cin, k, k, dtype=torch.float32, device=dev)
-                    wpad[:cout, :wsrc.shape[1]] = wsrc
-                    wsrc = wpad
-                wd = _new(dev, wsrc.numel())
-                _hip.check(L.y2_pack_weight(_hip.ptr(wsrc), _hip.ptr(wd), cop, cin, k, 1, st), 'y2_pack_weight')
-            dx = _new(dev, B, op.h, op.w, cin)
-            if op.stride == 1:
-                _gen_conv(L, st, dz, wd, dx, B, ho, wo, cop, cop, cin, k, 1, k - 1 - op.pad)
-            else:
-                _gen_conv(L, st, dz, wd, dx, B, ho, wo, cop, cop, cin, k, op.stride, op.pad, transposed=True, out_hw=(op.h, op.w))
-            G.setdefault(id(op.x), []).append(dx)
-        # ---- affine-parameter gradients: fp64 sums -> fp32, one launch; straight into the data-parallel bucket slices when there are any
-        items, handed, gb_all = [], [], None
-        for prm, o, ln in affine:
-            t = buffer_hook(prm) if buffer_hook is not None else None
-            if t is None:
-                if gb_all is None:
-                    gb_all = _new(dev, sums_arena.numel())
-                    items.append((_hip.MULTI_F64_TO_F32, gb_all, sums_arena))
-                t = gb_all[o:o + ln]
-            else:
-                items.append((_hip.MULTI_F64_TO_F32, t, sums_arena[o:o + ln]))
-            handed.append((prm, t))
-        _hip.multi(items, st)
-        for prm, t in handed:
-            ready(prm, t)
-        dx_img = None
-        if ctx.need_dx:
-            gx = G.pop(id(ctx.x4), None)
-            if gx:
-                dx_img = gx[0][..., :ctx.cin0].permute(0, 3, 1, 2).contiguous()
-        out = [None, dx_img, None]
-        for pid in ctx.param_ids:
-            out.append(grads.get(pid))
-        ctx.ops = None
-        ctx.prepared = None
-        return tuple(out)
-
-
 # ------------------------------------------------------------------------------------------------ a training step as a plan
 # The reference's step is three Python calls - `_inference`, `loss`, `loss_total.backward()` (train.py:344-351) - and on the autograd
 # path above every one of the ~270 kernels behind them is a ctypes call issued from Python, one by one, every step: 6-18 ms of host
@@ -1968,7 +1197,7 @@ class StepPlan(object):
                 head = _darknet_fwd(tape, dnn, st['x'], self.params, False, scope=self.scope if seg is not None else None)
             else:
                 tape.scope = self.scope if seg is not None else None
-                head = ResNetTrainFn.forward(tape, dnn, st['x'], False, *self.params)
+                head = train_oplist.OpListTrainFn.forward(tape, dnn, st['x'], False, *self.params)
             B, rows, cols, _ = head.shape
             dt, lt = _Tape(), _Tape()
             iou, co, sn, mn, mx, logits = DecodeFn.forward(dt, head, anchors_dev, A)
@@ -1987,7 +1216,7 @@ class StepPlan(object):
             if self.darknet:
                 _darknet_bwd(tape, df)
             else:
-                ResNetTrainFn.backward(tape, df)
+                train_oplist.OpListTrainFn.backward(tape, df)
         finally:
             dnn.grad_ready_hook, dnn.grad_buffer_hook = hooks
         missing = [p for p in self.params if p.requires_grad and id(p) not in grads]

@@ -480,11 +480,11 @@ class Tiny(Darknet):
 
     def forward(self, x):
         if self.training:
-            from model import train_graph
-            return train_graph.tiny_forward(self, x)
+            from model import train_oplist
+            return train_oplist.forward(self, x)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_graph
-            return train_graph.tiny_forward(self, x, frozen=True)      # differentiable eval mode: the op-list graph with frozen statistics
+            from model import train_oplist
+            return train_oplist.forward(self, x, frozen=True)      # differentiable eval mode: the op-list graph with frozen statistics
         with torch.no_grad():
             out = self.forward_nhwc(x)
         return out.permute(0, 3, 1, 2)
