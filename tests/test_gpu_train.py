@@ -429,6 +429,128 @@ def test_darknet_training_step_matches_oracle_autograd(bn):
     print('worst relative gradient error', worst)
 
 
+def _kernel_names(fn):
+    """Names of the library kernels `fn` launches (the per-launch event hooks of include/yolo2_hip.h: y2_prof_*)."""
+    import _hip
+    L = _hip.lib()
+    torch.cuda.synchronize()
+    L.y2_prof_enable(1)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        L.y2_prof_enable(0)
+    name, ms, fl = ctypes.create_string_buffer(96), ctypes.c_float(), ctypes.c_double()
+    return [name.value.decode() for i in range(L.y2_prof_count()) if L.y2_prof_get(i, name, 96, ctypes.byref(ms), ctypes.byref(fl)) == 0]
+
+
+def test_backward_keeps_its_decisions_when_the_table_changes_in_mid_pass(monkeypatch):
+    """The backward decides once per pass (model.train_graph._decide_bwd): the deep blocks here take y2_bn_act_bwd_wino6 - no dz, both 4x4-tile
+    transforms instead - and a table that changes while the pass runs (the data-parallel wrapper's import_tune arrives through grad_ready_hook;
+    here: both gradient pins flipped to the direct kernels at the first finished gradient) must not take the kernels those operands were built
+    for away from under them.  Every parameter gradient of the undisturbed and of the disturbed step against the oracle's fp64 autograd.
+
+    Before the pass decided once, the disturbed step ended in "RuntimeError: _conv: a transformed input serves the 4x4-tile form only"."""
+    import _hip
+    import model
+    from model import train_graph
+    widths = dict(NARROW)
+    widths['layers1.5'] = 8
+    widths.update({k: 128 for k in widths if k.startswith('layers2.') or k == 'layers3.0'})          # deep maps 8x8, wide enough for the 4x4-tile forms
+    sd = odark.init_state_dict(5, 20, seed=0, channels=widths, head_scale=1 / 8.0)
+    inf, anchors = build(sd)
+    inf.train()
+    S, B = 256, 2
+    x = synth.images(B, S, seed=1)
+    data = synth.norm_data(synth.labels(B, S, 20, seed=2), S, S, S // 32, S // 32)
+    # ---- the reference: the oracle's autograd, in fp64.  LeakyReLU has no derivative at 0, and among the ~10^6 activations of this shape some lie
+    # closer to 0 than any fp32 forward pass can resolve: there fp64 autograd picks a side that an fp32 evaluation need not be on, and ONE such
+    # element under a large gradient moves every gradient below it by 5 % and more (layers3.0 channel 31: |y| = 1.8e-5 in fp64, while the oracle's
+    # own fp32 forward is 5.9e-5 off in that layer; the atomics' order alone can flip it from run to run).  Which elements those are is decided
+    # by the ORACLE alone: |y| in fp64 within 4 x the largest difference between its own fp32 and fp64 forward in that layer (two fp32 evaluations
+    # differ by up to twice that error; twice again for margin).  There, and only there, the derivative is taken on the side that the forward
+    # of the very pass under test was on; the oracle's fp32 run, which gives the floor, is held to the same sides, and the floor must stay small.
+    t32, t64 = {}, {}
+    with torch.no_grad():
+        odark.forward(x, sd, training=True, taps=t32)
+        odark.forward(x.double(), {k: v.double() for k, v in sd.items()}, training=True, taps=t64)
+    pre = lambda a: torch.where(a > 0, a, a / odark.LEAKY)          # the pre-activation of a LeakyReLU output
+    layers = [k for k in t64 if k != odark.HEAD]
+    unplaced = {k: pre(t64[k]).abs() <= 4 * (pre(t32[k].double()) - pre(t64[k])).abs().max() for k in layers}
+    assert sum(int(m.sum()) for m in unplaced.values()) <= 1e-4 * sum(m.numel() for m in unplaced.values())          # (21 of 1.2 million here)
+
+    def oracle_grads(dtype, side):
+        """The oracle's autograd in `dtype`, LeakyReLU at the unplaced elements on the side `side` names."""
+        calls = iter(layers)
+
+        class _F(object):
+            def __getattr__(self, name):
+                return getattr(F, name)
+
+            @staticmethod
+            def leaky_relu(y, slope):
+                k = next(calls)
+                return y * torch.where(torch.where(unplaced[k], side[k], y > 0), torch.ones_like(y), torch.full_like(y, slope))
+        sdx = {k: v.detach().clone().to(dtype).requires_grad_('running' not in k) if v.is_floating_point() else v for k, v in sd.items()}
+        with monkeypatch.context() as m:
+            m.setattr(odark, 'F', _F())
+            lo, _ = oloss.loss(anchors.to(dtype), {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in data.items()},
+                               ohead.decode(odark.forward(x.to(dtype), sdx, training=True), anchors.to(dtype)), 0.6)
+            oloss.total(lo).backward()
+        return {k: v.grad for k, v in sdx.items() if v.requires_grad}
+    ours = dict(inf.dnn.named_parameters())
+    sides = []          # per backward pass under test: the side of every activation in ITS forward (the blocks it saved)
+    real_bwd = train_graph._darknet_bwd
+
+    def spy(ctx, dout):
+        sides.append({b.name: ((b.z * b.scale + b.shift) > 0).permute(0, 3, 1, 2).cpu() for b in ctx.blocks if b.name in unplaced})
+        return real_bwd(ctx, dout)
+    monkeypatch.setattr(train_graph, '_darknet_bwd', spy)
+
+    def step():
+        for p in ours.values():
+            p.grad = None
+        pred = model._inference(inf, x.to(dev()))
+        loss, _ = model.loss(anchors, data, pred, 0.6)
+        sum(loss[k] * oloss.HPARAM[k] for k in loss).backward()
+    refs = {}
+
+    def check(what, got, side):
+        assert sorted(side) == sorted(layers)
+        key = tuple(bool(v) for k in layers for v in side[k][unplaced[k]])
+        if key not in refs:
+            refs[key] = (oracle_grads(torch.float64, side), oracle_grads(torch.float32, side))
+        ref, ref32 = refs[key]
+        for k, v in ref.items():
+            assert got[k] is not None, (what, k)
+            e, floor = rel(got[k], v), rel(ref32[k], v)
+            print(what, k, 'error %.2e fp32 floor %.2e' % (e, floor))
+            assert floor <= 5 * GRAD_TOL, (what, k, floor)          # the oracle's own fp32 run agrees with the reference: no misplaced element hides in the floor
+            assert e <= max(GRAD_TOL, 2.5 * floor), (what, k, e, floor)
+    monkeypatch.setattr(_hip, 'AUTOTUNE', False)
+    monkeypatch.setattr(_hip, 'FORCE_GRAD', 'f43')
+    monkeypatch.setattr(_hip, 'FORCE_WGRAD', 'f34')
+    names = _kernel_names(step)
+    assert names.count('bn_bwd_wino6_kernel') >= 1, sorted(set(names))          # the fused path really ran: without it the rest proves nothing
+    undisturbed = {k: p.grad for k, p in ours.items()}
+    calls = []
+
+    def table_changes(param, grad):
+        if not calls:
+            _hip.FORCE_WGRAD = _hip.FORCE_GRAD = 'direct'
+        calls.append(param)
+    inf.dnn.grad_ready_hook = table_changes
+    try:
+        step()          # (before this pass decided once: RuntimeError, a transformed gradient serves the 4x4-tile form only)
+        torch.cuda.synchronize()
+    finally:
+        inf.dnn.grad_ready_hook = None
+        _hip.FORCE_GRAD, _hip.FORCE_WGRAD = 'f43', 'f34'
+    assert len(calls) > 2 and len(sides) == 2
+    check('undisturbed', undisturbed, sides[0])
+    check('table changed in mid-backward', {k: p.grad for k, p in ours.items()}, sides[1])
+
+
 @pytest.mark.parametrize('bn', [False, True])
 def test_eval_caches_follow_raw_pointer_writers(bn):
     """Packed / folded / Winograd-transformed weights are cached per parameter version, but the fused optimizer (and y2_bn_finalize)

@@ -179,3 +179,159 @@ def test_oplist_builder_selection_names_an_unknown_class():
     assert train_oplist._builder(object.__new__(model.resnet.ResNet)) is train_oplist._build_resnet
     with pytest.raises(TypeError, match=r'no training-graph builder for torch\.nn\.modules\.linear\.Linear'):
         train_oplist._builder(nn.Linear(1, 1))
+
+
+# ---- the backward's decisions: taken once per pass (model.train_graph._decide_bwd), applied - not looked up again - by _hip.conv_wgrad / autotune_conv
+def _darknet19_geometry(tg, _hip, B=64, S=416):
+    """[_Geo] of the full-width Darknet-19 at SxS, from the oracle's layer table (prepared operands everywhere but the first layer and the head)."""
+    from oracle import darknet as odark
+    rows, h, c = [], S, 3                        # (name, H, cin, cout, k, pool)
+    for j, item in enumerate(odark.LAYERS1):
+        if item == 'M':
+            continue
+        name, k, cout = item
+        pool = odark.LAYERS1[j + 1:j + 2] == ['M'] or name == odark.LAYERS1[-1][0]          # (layers2's leading pool belongs to layers1[-1])
+        rows.append((name, h, c, cout, k, pool))
+        h, c = (h // 2 if pool else h), cout
+    n1, c_pt = len(rows), odark.PASSTHROUGH[2]
+    rows.append(('passthrough', 2 * h, c, c_pt, 1, False))
+    for name, k, cout in odark.LAYERS2[1:] + [(odark.LAYERS3[0][0], odark.LAYERS3[0][1], odark.LAYERS3[0][2]), ('layers3.1', 1, 125)]:
+        cin = 4 * c_pt + c if name == 'layers3.0' else c
+        rows.append((name, h, cin, cout, k, False))
+        c = cout
+    names = [r[0] for r in rows]
+    routes, full, pooled = tg._routes(names, [r[5] for r in rows], n1, c_pt)
+    geo = [tg._Geo(H, H, cin, cout, k, cin, i == 0, False, False, None if (i == 0 or cout % 4) else bool(_hip.wino_eligible(cin, cout, k)), full[i], pooled[i])
+           for i, (name, H, cin, cout, k, pool) in enumerate(rows)]
+    return names, geo
+
+
+def _wgrad_key(g, B=64):
+    return ('wgrad', B, g.H, g.W, g.cin, g.ldx, g.cout, g.cout, False, 'cuda:0')
+
+
+def _dgrad_key(g, B=64):          # the data gradient of a block is a convolution with the roles of Cin and Cout exchanged, offered the 4x4-tile form
+    return (B, g.H, g.W, g.cout, g.cout, g.cin, 3, True, False, False, 0, 0, 0, False, 0, 0, 0, 'cuda:0', True, True, 'f43')
+
+
+@pytest.fixture
+def tune_defaults(monkeypatch):
+    """An empty algorithm table, nothing pinned, every A/B switch at its default."""
+    import _hip
+    from model import train_graph as tg
+    for name, value in (('_TUNE', {}), ('_DEFAULTS_SEEN', {'cuda:0': 0}), ('TUNE_CACHE', None), ('AUTOTUNE', True), ('DETERMINISTIC', False), ('WINOGRAD', True), ('IMPLICIT', True),
+                        ('PERSIST', True), ('SPLIT', ''), ('FORCE_ALGO', None), ('FORCE_GRAD', None), ('FORCE_WGRAD', None)):
+        monkeypatch.setattr(_hip, name, value)
+    for name, value in (('FUSE_CONV0', True), ('FUSE_WINO6', True), ('GRAD_F43', True), ('DEBUG_TAP', None)):
+        monkeypatch.setattr(tg, name, value)
+    return _hip, tg
+
+
+def test_backward_decisions_are_taken_once_from_the_table(tune_defaults, monkeypatch):
+    _hip, tg = tune_defaults
+    names, geo = _darknet19_geometry(tg, _hip)
+    assert len(geo) == 23 and names[-2:] == ['layers3.0', 'layers3.1'] and geo[-2].cin == 1280 and geo[13].H == 26 and geo[14].H == 13
+    deep = [i for i, g in enumerate(geo) if (g.H, g.cin, g.cout, g.k) == (13, 512, 1024, 3)]
+    assert [names[i] for i in deep] == ['layers2.1', 'layers2.3', 'layers2.5']
+    for i in deep:
+        _hip._TUNE[_wgrad_key(geo[i])] = 2
+        _hip._TUNE[_dgrad_key(geo[i])] = [6, 5]
+    plans = tg._decide_bwd(geo, 64, 'cuda:0')
+    assert [i for i, p in enumerate(plans) if p.fused6] == deep and all(plans[i].fused6 == (6, 5) and plans[i].wgrad == 2 and not plans[i].zero for i in deep)
+    assert plans[0] == tg._Plan(0, True, True, True, None, None)                                  # the first layer: its own kernel, dz formed inside it
+    assert not tg._decide_bwd(geo, 64, 'cuda:0', need_dx=True)[0].fuse0
+    for i, (g, p) in enumerate(zip(geo, plans)):
+        if i and g.k == 3 and i not in deep:                                                # no entry: unknown - and NOT in the zero fill as if it were choice 0
+            assert p.wgrad is None and not p.zero and not p.final and p.fused6 is None, names[i]
+        if g.k == 1:                                                                        # the direct kernel: accumulates; [cout][1][cin] is the gradient's layout
+            assert p.wgrad == 0 and p.zero and p.final == (g.cout % 4 == 0) and p.fused6 is None, names[i]
+    # the records are values, not views of the table
+    kept = list(plans)
+    _hip._TUNE.clear()
+    monkeypatch.setattr(_hip, 'FORCE_WGRAD', 'direct')
+    assert plans == kept and plans[deep[0]].wgrad == 2 and plans[deep[0]].fused6 == (6, 5)
+    # pinned to the direct kernel (a table that says otherwise does not count): every 3x3 target is zero filled, nothing is fused
+    for i in deep:
+        _hip._TUNE[_wgrad_key(geo[i])] = 2
+        _hip._TUNE[_dgrad_key(geo[i])] = [6, 5]
+    direct = tg._decide_bwd(geo, 64, 'cuda:0')
+    assert all(p.zero and p.wgrad == 0 for g, p in zip(geo, direct) if g.k == 3) and not any(p.fused6 for p in direct)
+    # a table that offers both 4x4-tile forms EVERYWHERE: the pooled blocks, the reorg source and the head still never take the fused form
+    monkeypatch.setattr(_hip, 'FORCE_WGRAD', None)
+    for g in geo[1:]:
+        _hip._TUNE[_wgrad_key(g)] = 2
+        _hip._TUNE[_dgrad_key(g)] = [6, 5]
+    wide = tg._decide_bwd(geo, 64, 'cuda:0')
+    fused = [names[i] for i, p in enumerate(wide) if p.fused6]
+    assert fused == ['layers1.8', 'layers1.12', 'layers1.14'] + ['layers2.%d' % j for j in (1, 3, 5, 6, 7)] + ['layers3.0']
+    assert not any(p.fused6 for g, p in zip(geo, wide) if g.pooled or g.full != 0 or g.k == 1) and any(g.pooled and p.wgrad == 2 for g, p in zip(geo, wide))
+    for flag, holder in (('FUSE_WINO6', tg), ('DETERMINISTIC', _hip), ('SPLIT', _hip)):     # the A/B switch, the deterministic and the split modes: never
+        monkeypatch.setattr(holder, flag, not getattr(holder, flag))
+        assert not any(p.fused6 for p in tg._decide_bwd(geo, 64, 'cuda:0')), flag
+        monkeypatch.setattr(holder, flag, not getattr(holder, flag))
+
+
+class _Recorder(object):
+    """Stands in for _hip.lib(): records the entry points asked for; they run when `real` is given, else return `rc`."""
+
+    def __init__(self, real=None, rc=0):
+        self.real, self.rc, self.names = real, rc, []
+
+    def __getattr__(self, name):
+        self.names.append(name)
+        return getattr(self.real, name) if self.real is not None else (lambda *a: self.rc)
+
+
+@pytest.mark.parametrize('B,hw,cin,want', [(2, 13, 1024, (6, 5)), (32768, 52, 1024, (0, 0))])          # accepted; refused on size (tiles x Cin >= 2^32)
+def test_peek_equals_launch_under_the_pinned_gradient_algorithm(tune_defaults, monkeypatch, B, hw, cin, want):
+    import torch
+    _hip, tg = tune_defaults
+    monkeypatch.setattr(_hip, 'FORCE_GRAD', 'f43')
+    rec = _Recorder(_hip.lib())
+    monkeypatch.setattr(_hip, 'lib', lambda: rec)
+    monkeypatch.setattr(_hip, 'workspace', lambda *a: pytest.fail('scratch allocated'))
+    operand = torch.zeros(4)
+
+    def never():
+        pytest.fail('the 4x4-tile operand was built for a question')
+    p = tg._problem(B, hw, hw, cin, cin, 512, 3, 512)
+    assert _hip.autotune_conv(p, 'cuda:0', f43=never, wino_eligible=True, peek=True) == want and (p.algo, p.tile, p.w) == (0, 0, None)
+    p.w = None          # a pruned step: no packed weight at hand - a missing operand is not a refusal
+    assert _hip.autotune_conv(p, 'cuda:0', f43=lambda: operand, wino_eligible=True) == want and (p.algo, p.tile) == want
+    assert p.w == (operand.data_ptr() if want[0] == 6 else None)
+    assert set(rec.names) == {'y2_conv_fwd_workspace_bytes'} and len(rec.names) == 2
+    # a decision handed in is applied without a question
+    assert _hip.autotune_conv(p, 'cuda:0', f43=lambda: operand, wino_eligible=True, choice=(6, 3)) == (6, 3) and (p.algo, p.tile) == (6, 3) and len(rec.names) == 2
+    with pytest.raises(_hip.OperandMissing):
+        _hip.autotune_conv(p, 'cuda:0', wino_eligible=True, choice=(1, 5))
+
+
+def test_conv_wgrad_runs_the_choice_it_is_given(tune_defaults, monkeypatch):
+    import torch
+    _hip, tg = tune_defaults
+    rec = _Recorder(rc=4096)          # (a workspace size; the launches' return codes go through the patched check)
+    monkeypatch.setattr(_hip, 'lib', lambda: rec)
+    monkeypatch.setattr(_hip, 'check', lambda rc, what: None)
+    monkeypatch.setattr(_hip, 'stream', lambda: None)
+    B, H, C = 2, 8, 64
+    x, dz, out, native = torch.zeros(B, H, H, C), torch.zeros(B, H, H, C), torch.zeros(C * 9 * C), torch.zeros(C, C, 3, 3)
+    key = ('wgrad', B, H, H, C, C, C, C, False, 'cpu')
+    launch = {0: 'y2_conv_wgrad', 1: 'y2_wino_wgrad', 2: 'y2_wino_wgrad_ex'}
+
+    def run(**kw):
+        del rec.names[:]
+        got = _hip.conv_wgrad(x, dz, B, H, H, C, C, C, C, 3, out=out, **kw)
+        return got, [n for n in rec.names if 'workspace' not in n]
+    for choice in (0, 1, 2):
+        for table in ({}, {key: (choice + 1) % 3}, {key: (choice + 2) % 3}):          # empty (a lookup would MEASURE), and holding each other answer
+            monkeypatch.setattr(_hip, '_TUNE', dict(table))
+            assert run(choice=choice, zeroed=True) == (out, [launch[choice]])
+            assert run(choice=choice) == (out, (['y2_multi'] if choice == 0 else []) + [launch[choice]])          # the fill: the library's, on the launch stream
+            got, names = run(choice=choice, zeroed=True, native=native)
+            assert names == ['y2_wino_wgrad_ex' if choice else 'y2_conv_wgrad'] and got is (native if choice else out)
+        monkeypatch.setattr(_hip, '_TUNE', {key: choice})
+        assert run() == run(choice=choice)                                              # not given: looked up, as before
+    monkeypatch.setattr(_hip, 'wgrad_choice', lambda *a: pytest.fail('the table was read'))
+    assert run(choice=2, dz_pre=True, native=native) == (native, ['y2_wino_wgrad_ex'])
+    with pytest.raises(AssertionError):
+        run(choice=0, dz_pre=True)                                                      # a transformed gradient serves the 4x4-tile form only

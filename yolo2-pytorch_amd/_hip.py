@@ -577,7 +577,7 @@ class OperandMissing(RuntimeError):
     warm-up passes used: model.train_graph)."""
 
 
-def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, split_plane=0, f43=None, wino_eligible=None, peek=False):
+def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, split_plane=0, f43=None, wino_eligible=None, peek=False, choice=None):
     """Measure-don't-guess algorithm + tile selection for one y2_conv_fwd problem: the first time a problem shape is seen,
     every tile configuration of the direct kernel - and, when `wino_w` (y2_wino_weight output) is given, of the Winograd
     path - is timed (HIP events, best of 2 x 3 launches) and the fastest is cached for the process; later calls only
@@ -586,7 +586,10 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
     implicit_ok=False: the caller wants the transformed input left in the workspace (training keeps it for the weight gradient),
     so the algorithm that never materialises it (3) is not offered.
     f43: the result is a GRADIENT and may take Winograd F(4x4,3x3) (Y2_ALGO_WINOGRAD_F43, 8-9e-6 x rms per layer): the y2_wino6_weight operand
-    or a callable producing it (called only when that algorithm is timed or chosen)."""
+    or a callable producing it (called only when that algorithm is timed or chosen).
+    peek=True: the (algo, tile) this problem is KNOWN to take - pinned by Y2_FORCE_GRAD_ALGO, or in the table - else None (Y2_FORCE_ALGO, the
+    deterministic mode, the static preferences): nothing is measured, allocated or written to params (its pointers may be dummies).  A call without
+    peek is that lookup, then measure-if-unknown, then apply.  choice=(algo, tile): a decision taken earlier is applied (operand checks, lifetime rule), not looked up."""
     # wino_eligible: the layer IS Winograd-eligible although `wino_w` is not at hand (None) - the problem keeps its identity (the key below),
     # and an algorithm that reads the missing operand raises OperandMissing instead of being silently replaced by another one
     wino_ok = (((wino_w is not None) if wino_eligible is None else bool(wino_eligible)) and WINOGRAD and params.ksize == 3 and params.stride in (0, 1)
@@ -602,17 +605,6 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
         if not f43_t:
             f43_t.append(f43() if callable(f43) else f43)
         return f43_t[0]
-    if peek:
-        # the answer a later call with the same problem will get, when it is already known (pinned, or in the table): (algo, tile) or None.  Nothing is
-        # measured, nothing is written to params
-        if FORCE_GRAD is not None and f43 is not None:
-            return (6, 5) if (FORCE_GRAD == 'f43' and f43_ok) else (0, 0)
-        if FORCE_ALGO is not None or DETERMINISTIC:
-            return None
-        if str(dev) not in _DEFAULTS_SEEN:
-            load_tune_defaults(dev)
-        hit = _TUNE.get(key)
-        return None if hit is None else (tuple(hit) if isinstance(hit, (list, tuple)) else (0, hit))
     implicit_ok = bool(implicit_ok and IMPLICIT) and params.Cin % 32 == 0
     w_direct = params.w
 
@@ -627,13 +619,34 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
         # workspace that grows in between would be handed the freed block): the tensor rides on the params object
         params._f43_operand = f43_t if algo == 6 else None
         return choice
-    if FORCE_GRAD is not None and f43 is not None:
-        # a data gradient under a pinned gradient algorithm (no measurement, no cache)
-        if FORCE_GRAD == 'f43' and f43_ok:
-            apply((6, 5))
-            if lib().y2_conv_fwd_workspace_bytes(ctypes.byref(params)) >= 0:
-                return (6, 5)
+
+    def first_accepted(cands):
+        for c in cands:
+            apply(c)
+            if lib().y2_conv_fwd_workspace_bytes(ctypes.byref(params)) >= 0:      # the library accepts this problem (sizes, alignment)
+                return c
         return apply((0, 0))
+
+    def known():
+        if FORCE_GRAD is not None and f43 is not None:
+            # a data gradient under a pinned gradient algorithm.  The library is asked about a COPY with aligned dummies: a missing operand is no refusal
+            q = ConvParams.from_buffer_copy(params)
+            q.algo, q.tile, q.x, q.w, q.y = 6, 5, q.x or 256, 256, q.y or 256
+            return (6, 5) if (FORCE_GRAD == 'f43' and f43_ok and lib().y2_conv_fwd_workspace_bytes(ctypes.byref(q)) >= 0) else (0, 0)
+        if FORCE_ALGO is not None:
+            return None
+        if str(dev) not in _DEFAULTS_SEEN:
+            load_tune_defaults(dev)
+        hit = None if DETERMINISTIC else _TUNE.get(key)      # deterministic mode ignores measured choices (they may differ between runs)
+        hit = None if hit is None else (tuple(hit) if isinstance(hit, (list, tuple)) else (0, hit))
+        # Y2_CONV_PERSIST=0 (A/B switch): a table entry that names a persistent tile does not count - measure (or fall back) without them
+        return hit if (hit is None or PERSIST or not (hit[0] == 0 and hit[1] in (11, 12, 13, 15))) else None
+    if choice is None:
+        choice = known()
+    if peek:
+        return choice
+    if choice is not None:
+        return apply(tuple(choice))
     if FORCE_ALGO is not None:
         # deterministic algorithm coverage (tests, A/B runs): every eligible layer takes the named algorithm, everything else the
         # direct kernel with the library's own tile choice; no measurement, no cache
@@ -642,19 +655,7 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
             want = (2, want[1])         # where the transformed input must stay behind: the fused kernel that reads it
         if want is not None and want[0] in (4, 5) and not split_ok:
             want = (1, 5) if wino_ok else None
-        if want is not None and wino_ok and (want[0] == 1 or params.Cin % 32 == 0):
-            apply(want)
-            if lib().y2_conv_fwd_workspace_bytes(ctypes.byref(params)) >= 0:
-                return want
-        return apply((0, 0))
-    if str(dev) not in _DEFAULTS_SEEN:
-        load_tune_defaults(dev)
-    hit = None if DETERMINISTIC else _TUNE.get(key)      # deterministic mode ignores measured choices (they may differ between runs)
-    if hit is not None:
-        hit = tuple(hit) if isinstance(hit, (list, tuple)) else (0, hit)
-        if PERSIST or not (hit[0] == 0 and hit[1] in (11, 12, 13, 15)):
-            return apply(hit)
-        # Y2_CONV_PERSIST=0 (A/B switch): a table entry that names a persistent tile does not count - measure (or fall back) without them
+        return first_accepted([want] if (want is not None and wino_ok and (want[0] == 1 or params.Cin % 32 == 0)) else [])
     if not AUTOTUNE or DETERMINISTIC or torch.cuda.is_current_stream_capturing():
         # no measurement possible (or, deterministic mode: a timed choice may differ from run to run and with it the rounding): the choices the measurements converge to on MI355X (profiles/r01_detect_b32_layer_table.txt)
         prefer = []
@@ -670,14 +671,9 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
             prefer.append((2, 0))       # fused Winograd on the 104x104 ... 26x26 layers
         if wino_ok and params.Cin >= 128:
             prefer.append((1, 5))       # three-kernel Winograd, 64x128 GEMM tiles, on the 13x13 layers
-        for choice in prefer:
-            apply(choice)
-            if lib().y2_conv_fwd_workspace_bytes(ctypes.byref(params)) >= 0:      # the library accepts this problem (sizes, alignment)
-                return choice
-        return apply((0, 0))
+        return first_accepted(prefer)
     L = lib()
     st = stream()
-    TUNE_MISSES.append(key)           # a problem shape neither this process nor the committed table has met: measured now (bench.py reports the count per leg)
     big = params.B * params.H * params.W >= 65536 and params.Cout >= 128 and params.ksize in (1, 3) and params.stride in (0, 1) \
         and params.pad_plus1 in (0, (params.ksize - 1) // 2 + 1) and not params.transposed and not params.residual
     cands = [(0, t) for t in [5, 3, 2, 1] + ([6] if params.Cout <= 32 else []) + ([8, 9] if big else [])]      # 8, 9: 512-thread 256x128 / 128x256 tiles
@@ -710,10 +706,8 @@ def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, s
         if t < best_t:
             best, best_t = choice, t
     params.stats = stats_save
-    apply(best)
-    _TUNE[key] = list(best)
-    _tune_save()
-    return best
+    tune_store(key, list(best))       # a problem shape neither this process nor the committed table had met (TUNE_MISSES: bench.py reports the count per leg)
+    return apply(best)
 
 
 def tune_lookup(key, dev):
@@ -780,7 +774,7 @@ def wgrad_choice(B, H, W, cin, ldx, cout, ldz, k, has_v, dev):
     """Which kernel conv_wgrad will run for this problem: 0 = y2_conv_wgrad (accumulates into a ZEROED buffer), 1 = y2_wino_wgrad
     (2x2 gradient tiles; overwrites), 2 = its 4x4-tile form (Winograd F(3x3, 4x4): fewer multiply-adds, never reads the forward's
     transformed input; overwrites), None = eligible for all and not measured yet (conv_wgrad will time them and zero the buffer itself)."""
-    if not (wino_eligible(cout, cin, k) and not (ldx % 4) and not (ldz % 4)):
+    if not eligible_wino(cout, cin, k, ldx, ldz):
         return 0
     if FORCE_WGRAD is not None and not DETERMINISTIC:
         return {'direct': 0, 'wino': 1, 'f34': 2}[FORCE_WGRAD]
@@ -809,49 +803,47 @@ def _wgrad_scratch(dev, need):
 
 
 def eligible_wino(cout, cin, k, ldx, ldz):
-    return wino_eligible(cout, cin, k) and not (ldx % 4) and not (ldz % 4)
+    return bool(wino_eligible(cout, cin, k) and not (ldx % 4) and not (ldz % 4))
 
 
-def conv_wgrad(x, dz, B, H, W, cin, ldx, cout, ldz, k, v=None, out=None, zeroed=False, native=None, dz_pre=False):
+def conv_wgrad(x, dz, B, H, W, cin, ldx, cout, ldz, k, v=None, out=None, zeroed=False, native=None, dz_pre=False, choice=None):
     """Packed weight gradient dw[cout][k*k][cin] of a stride-1 "same" convolution: y2_conv_wgrad (9 shifted reductions
     over pixels) or, for 3x3 layers where it measures faster, y2_wino_wgrad (16 reductions over 2x2 tiles).  The choice
     is timed once per problem shape and cached.  `v`: the layer's transformed input kept from a Winograd forward (see
     include/yolo2_hip.h, y2_wino_wgrad) - the weight gradient then skips its input transform.  `out`: destination (cout*k*k*cin
     floats) instead of a fresh tensor; `zeroed`: the caller has zero-filled it (one y2_multi launch for all layers of a step).
-    `native`: a [cout][cin][3][3] destination; when the (already measured) choice is the Winograd reduction it is written directly in
-    that layout and returned INSTEAD of the packed buffer (the caller checks `result is native`)."""
+    `native`: a [cout][cin][3][3] destination; when the choice is the Winograd reduction it is written directly in that layout and
+    returned INSTEAD of the packed buffer (the caller checks `result is native`).
+    `choice`: what wgrad_choice answered when the caller planned this launch (0, 1, 2): exactly that kernel runs, the table is not read again.
+    None (not given, or unmeasured then): looked up here, measured when unknown and not capturing.  Fills and launches go to the launch stream."""
     L, st, dev = lib(), stream(), x.device
     nw = cout * cin * k * k
-    choice = wgrad_choice(B, H, W, cin, ldx, cout, ldz, k, v is not None, dev)
-    if dz_pre:
-        # `dz` is the transformed gradient [36][T][cout] of the 4x4-tile form (y2_bn_act_bwd_wino6): the caller looked the choice up before it built it
-        if choice != 2:
-            raise RuntimeError('conv_wgrad: a transformed gradient serves the 4x4-tile form only (choice %r)' % (choice,))
-        need = L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, 6)
-        ws = _wgrad_scratch(dev, need)
-        dst = native if native is not None else (out if out is not None else torch.empty(nw, dtype=torch.float32, device=dev))
-        check(L.y2_wino_wgrad_ex(ptr(x), ptr(dz), ptr(dst), B, H, W, cin, ldx, cout, cout, None, ptr(ws), ws.numel() * 4, 7 if native is not None else 6, st), 'y2_wino_wgrad_ex')
+    eligible = eligible_wino(cout, cin, k, ldx, ldz)
+    if choice is None:
+        choice = wgrad_choice(B, H, W, cin, ldx, cout, ldz, k, v is not None, dev)
+    assert choice in (None, 0) or eligible
+
+    def wino_ex(dst, ld, mode, vt=None):          # scratch modes: 6 serves both forms that read a transformed gradient (6 packed, 7 native)
+        ws = _wgrad_scratch(dev, L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, min(mode, 6)))
+        check(L.y2_wino_wgrad_ex(ptr(x), ptr(dz), ptr(dst), B, H, W, cin, ldx, cout, ld, ptr(vt), ptr(ws), ws.numel() * 4, mode, st), 'y2_wino_wgrad_ex')
         return dst
-    eligible = wino_eligible(cout, cin, k) and not (ldx % 4) and not (ldz % 4)
-    key = ('wgrad', B, H, W, cin, ldx, cout, ldz, v is not None, str(dev))
+    if dz_pre:
+        # `dz` is the transformed gradient [36][T][cout] of the 4x4-tile form (y2_bn_act_bwd_wino6), built by a caller that had decided on that form
+        assert choice == 2, choice
+        if native is not None:
+            return wino_ex(native, cout, 7)
+        return wino_ex(out if out is not None else torch.empty(nw, dtype=torch.float32, device=dev), cout, 6)
     # the direct kernel accumulates split partial sums into a zeroed buffer; the Winograd path overwrites (no fill needed)
-    if native is not None and choice in (1, 2) and eligible_wino(cout, cin, k, ldx, ldz):
+    if native is not None and choice in (1, 2):
         assert native.numel() == nw and native.is_contiguous()
-        need = L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, 1 if choice == 1 else 3)
-        ws = _wgrad_scratch(dev, need)
-        check(L.y2_wino_wgrad_ex(ptr(x), ptr(dz), ptr(native), B, H, W, cin, ldx, cout, ldz, ptr(v) if choice == 1 else None, ptr(ws), ws.numel() * 4,
-                                 1 if choice == 1 else 3, st), 'y2_wino_wgrad_ex')
-        return native
+        return wino_ex(native, ldz, 1 if choice == 1 else 3, v if choice == 1 else None)
     dwp = out if out is not None else torch.empty(nw, dtype=torch.float32, device=dev)
     assert dwp.numel() >= nw and dwp.is_contiguous()
     if choice not in (1, 2) and not zeroed:
-        dwp.zero_()
+        multi([(MULTI_ZERO, dwp, None)], st)
 
     def direct():
         check(L.y2_conv_wgrad(ptr(x), ptr(dz), ptr(dwp), B, H, W, cin, ldx, cout, ldz, k, st), 'y2_conv_wgrad')
-    if not eligible:
-        direct()
-        return dwp
     ws = None
     if choice != 0:      # (a layer whose measured choice is the direct kernel needs no Winograd scratch: the 208x208 layer alone would size it at 4-9 GB)
         need = L.y2_wino_wgrad_workspace_bytes(B, H, W, cin, cout) if choice is None else L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, 2 if choice == 2 else 0)
@@ -887,11 +879,8 @@ def conv_wgrad(x, dz, B, H, W, cin, ldx, cout, ldz, k, v=None, out=None, zeroed=
                 # on the 104x104 layers it wins even so).  times are for two launches.
                 times[1] += 2.0 * 5.0 * B * H * W * cin * 4 / 5.5e9
             choice = times.index(min(times))
-            TUNE_MISSES.append(key)
-            _TUNE[key] = choice
-            _tune_save()
-            with _timing_stream():
-                dwp.zero_()          # the timing launches of the direct kernel accumulated into dwp
+            tune_store(('wgrad', B, H, W, cin, ldx, cout, ldz, v is not None, str(dev)), choice)
+            multi([(MULTI_ZERO, dwp, None)], st)          # the timing launches of the direct kernel accumulated into dwp
     (direct, wino, wino6)[choice]()
     return dwp
 

@@ -16,6 +16,7 @@ model/train_oplist.py, and both graphs are built from the parts in model/_train_
 
 torch only allocates, keeps the autograd tape and (in train.py's wrapper) runs the RCCL all-reduce.
 """
+import collections
 import ctypes
 import os
 
@@ -72,8 +73,22 @@ _WINO_CHUNK_BYTES = int(os.environ.get('Y2_WINO_CHUNK_MB', '4096')) << 20      #
 OperandPruned = _hip.OperandMissing      # a captured step prepares only the GEMM operands its warm-up passes used (StepPlan.used_last); the algorithm table asked for another one
 
 
+def _problem(B, H, W, cin, ldx, cout, k, ldy, coff=0, ldp=0, out_mode=0, slope=1.0):
+    """The y2_conv_params of one stride-1 "same" convolution with aligned dummies for x and y: enough to ask the algorithm table about it."""
+    p = _hip.ConvParams()
+    p.x = p.y = 256
+    p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, H, W, cin, ldx, cout, k
+    p.ldy, p.coff, p.ldp, p.poff, p.out_mode = ldy, coff, ldp, 0, out_mode
+    p.slope, p.tile = slope, 0
+    return p
+
+
+def _f43_offered(eligible, cin, H, W):          # a data gradient is offered the 4x4-tile Winograd form (the measurement decides: 13x13 ... 26x26 at 416, 19x19 ... 38x38 at 608)
+    return bool(GRAD_F43 and eligible and cin >= 128 and H * W <= 52 * 52)
+
+
 def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=None, slope=1.0, stats=None, y_pool=None, ldp=0, coff=0, out_mode=0, keep_v=False, u=False,
-          us=None, us_plane=0, grad=False, note=None, u_eligible=None, u6=None, peek=False, pre=None, dev=None):
+          us=None, us_plane=0, grad=False, note=None, u_eligible=None, u6=None, choice=None, pre=None, problem=None):
     """One y2_conv_fwd.  keep_v: when the Winograd algorithm is chosen, run it in a workspace of its own and return that tensor -
     its head is the transformed input V, which the weight gradient of the same layer reuses (y2_wino_wgrad v_transformed).
     u: the layer's Winograd filter transform when the caller prepared it (y2_prep_weights), None = not eligible, False = derive it here.
@@ -81,20 +96,13 @@ def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=No
     u = None with u_eligible = True (the layer is Winograd-eligible, its transform was not prepared: the problem keeps its identity in the
     algorithm table - same key, same offer of the 4x4-tile gradient form - and only a choice that READS u fails).
     note: callable('w' | 'u' | '6') told which filter operand the chosen algorithm reads (packed, 2x2-tile transform, 4x4-tile transform).
-    u6: the 4x4-tile transform when the caller prepared it; else it is derived from wp when that algorithm is timed or chosen."""
-    # peek: return the (algo, tile) this problem is known to take, or None - nothing is launched (x / y may be None).
-    # pre: the transformed input [36][T][cin] of the 4x4-tile form, built by y2_bn_act_bwd_wino6 because peek said the problem takes that form: the launch reads
-    # it instead of transforming x (which may be None then)
-    p = _hip.ConvParams()
+    u6: the 4x4-tile transform when the caller prepared it; else it is derived from wp when that algorithm is timed or chosen.
+    choice: the (algo, tile) decided for this problem earlier in the pass (_decide_bwd): applied, not looked up again.  pre: the transformed input
+    [36][T][cin] of the 4x4-tile form, built by y2_bn_act_bwd_wino6 on that decision: the launch reads it instead of transforming x (None then)."""
+    p = problem if problem is not None else _problem(B, H, W, cin, ldx, cout, k, ldy, coff, ldp, out_mode, slope)          # (problem: as _decide_bwd described it)
     p.x, p.w = (x.data_ptr() if x is not None else 256), (wp.data_ptr() if wp is not None else None)
-    p.scale = scale.data_ptr() if scale is not None else None
-    p.shift = shift.data_ptr() if shift is not None else None
-    p.y = y.data_ptr() if y is not None else (256 if peek else None)
-    p.y_pool = y_pool.data_ptr() if y_pool is not None else None
-    p.stats = stats.data_ptr() if stats is not None else None
-    p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, H, W, cin, ldx, cout, k
-    p.ldy, p.coff, p.ldp, p.poff, p.out_mode = ldy, coff, ldp, 0, out_mode
-    p.slope, p.tile = slope, 0
+    for field, t in (('scale', scale), ('shift', shift), ('y', y), ('y_pool', y_pool), ('stats', stats)):
+        setattr(p, field, t.data_ptr() if t is not None else None)
     # 3x3 layers: also offer the Winograd algorithm (filter transform of the packed weight: fprop and dgrad alike)
     if u is False:
         u = _hip.wino_weight(wp, cout, cin) if (out_mode == 0 and _hip.wino_eligible(cout, cin, k)) else None
@@ -109,14 +117,11 @@ def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=No
             raise OperandPruned('the 4x4-tile data-gradient operand is derived from a packed weight this step did not prepare')
         return _hip.wino6_weight(wp, cout, cin)
     eligible = (u is not None) if u_eligible is None else (bool(u_eligible) and out_mode == 0)
-    f43 = f43_operand if (grad and GRAD_F43 and eligible and cin >= 128 and H * W <= 52 * 52) else None      # (offered; the measurement decides: 13x13 ... 26x26 at 416, 19x19 ... 38x38 at 608)
-    dev = dev if dev is not None else (x if x is not None else (pre if pre is not None else y)).device
-    if peek:
-        return _hip.autotune_conv(p, dev, wino_w=u, implicit_ok=not keep_v, wino_split=us if u is not None else None, split_plane=us_plane, f43=f43, wino_eligible=eligible, peek=True)
-    _hip.autotune_conv(p, dev, wino_w=u, implicit_ok=not keep_v, wino_split=us if u is not None else None, split_plane=us_plane, f43=f43, wino_eligible=eligible)
+    dev = (x if x is not None else pre).device
+    _hip.autotune_conv(p, dev, wino_w=u, implicit_ok=not keep_v, wino_split=us if u is not None else None, split_plane=us_plane,
+                       f43=f43_operand if (grad and _f43_offered(eligible, cin, H, W)) else None, wino_eligible=eligible, choice=choice)
     if pre is not None:
-        if p.algo != 6:
-            raise RuntimeError('_conv: a transformed input serves the 4x4-tile form only (algorithm %d chosen)' % p.algo)
+        assert p.algo == 6, p.algo
         p.algo, p.x, p.ldx = 7, pre.data_ptr(), cin          # Y2_ALGO_WINOGRAD_F43_PRE
     if wp is None and (p.algo == 0 or (p.algo in (6, 7) and u6 is None)):
         raise OperandPruned('algorithm %d reads the packed weight, which this step did not prepare' % p.algo)
@@ -453,6 +458,62 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
     return cur
 
 
+# what _decide_bwd reads of one saved block.  ud_ok: its prepared data-gradient operands allow the Winograd forms (None: none prepared); full / pooled: _routes
+_Geo = collections.namedtuple('_Geo', 'H W cin cout k ldx first has_v padded ud_ok full pooled')
+_Plan = collections.namedtuple('_Plan', 'wgrad zero final fuse0 fused6 problem')
+
+
+def _routes(names, pools, n1, c_pt):
+    """Where the data gradient of block i goes: [(consumer block, it arrives as that block's POOLED gradient, channel offset, reorg mode)] per block; and
+    what arrives at each block: `full` (the reorg mode of its full-size gradient source, None without one; the head's is the loss) and `pooled`."""
+    idx = {name: i for i, name in enumerate(names)}
+    out, full, pooled = [[] for _ in names], [None] * (len(names) - 1) + [0], [False] * len(names)
+    for i, name in enumerate(names[1:], 1):
+        if name == 'layers3.0':             # the concat buffer [B,h,w,4*c_pt + c_l2]: reorg'ed channels first, then the last block of layers2
+            out[i] = [(idx['passthrough'], False, 0, 1), (i - 1, False, 4 * c_pt, 0)]
+        elif name == 'passthrough':
+            out[i] = [(n1 - 1, False, 0, 0)]
+        elif i == n1 + 1:                   # first conv of layers2: its input is the pooled layers1[-1]
+            out[i] = [(n1 - 1, True, 0, 0)]
+        else:
+            out[i] = [(i - 1, pools[i - 1], 0, 0)]
+    for j, is_pool, _, mode in sum(out, []):
+        if is_pool:
+            pooled[j] = True
+        else:
+            full[j] = mode
+    return out, full, pooled
+
+
+def _decide_bwd(geo, B, dev, need_dx=False):
+    """Every decision of one backward pass that something else in the pass depends on, taken ONCE, before the first launch, from the algorithm
+    table as it is now: one _Plan per block.  No GPU call, no allocation; the records are values - a table that changes while the pass runs (a
+    measurement in an earlier layer of the same shape, import_tune from the data-parallel wrapper) shows in the NEXT pass.
+    wgrad: _hip.wgrad_choice (0, 1, 2), None = unknown: it resolves at its launch (measured there), and what is prepared for it is right for any
+    outcome - dz is materialised, nothing is fused, the target is zero filled on the weight gradient's stream; zero: the target is in the step's one
+    zero fill; final: the target IS the gradient tensor (no unpack pass); fuse0: the first layer forms dz inside its weight gradient - no dz tensor
+    (1.4 GB at batch 64), no second pass; fused6: the (6, tile) data-gradient choice of a block that takes y2_bn_act_bwd_wino6, else None."""
+    plans = []
+    for g in geo:
+        cop = (g.cout + 3) // 4 * 4
+        if g.first:
+            small = g.cin <= 3 and g.cout <= 64          # y2_conv0_wgrad: writes the gradient's own layout, accumulating
+            # (model/yolo2.py:78-79: conv + pool, nothing below it needs a data gradient: only the weight gradient reads dz - from (z, dy_pool) and the pass-1 sums)
+            fuse0 = bool(FUSE_CONV0 and small and g.full is None and g.pooled and not (g.H & 1) and not (g.W & 15) and B * g.H * g.W * g.cout * 4 < 0xffff0000 and not need_dx)
+            plans.append(_Plan(0, small, small, fuse0, None, None))
+            continue
+        wgrad = _hip.wgrad_choice(B, g.H, g.W, g.cin, g.ldx, cop, cop, g.k, g.has_v, dev)
+        # weight AND data gradient KNOWN to run the 4x4-tile forms: y2_bn_act_bwd_wino6 writes their two transforms instead of dz
+        fused6 = problem = None
+        if (FUSE_WINO6 and wgrad == 2 and g.k == 3 and g.ud_ok is not None and not g.pooled and g.full == 0 and cop == g.cout and not g.padded
+                and DEBUG_TAP is None and not _hip.DETERMINISTIC and not _hip.split_mode()):
+            problem = _problem(B, g.H, g.W, cop, cop, g.cin, g.k, g.cin)          # described once: the launch fills in its pointers
+            hit = _hip.autotune_conv(problem, dev, f43=True if _f43_offered(g.ud_ok, cop, g.H, g.W) else None, wino_eligible=g.ud_ok, peek=True)
+            fused6 = tuple(hit) if (hit is not None and hit[0] == 6) else None
+        plans.append(_Plan(wgrad, wgrad == 0, g.k == 1 and cop == g.cout and not g.padded, False, fused6, problem if fused6 else None))      # (final: [cout][1][cin] IS the state_dict layout)
+    return plans
+
+
 def _darknet_bwd(ctx, dout):
     L = _hip.lib()
     st = _hip.stream()
@@ -469,13 +530,11 @@ def _darknet_bwd(ctx, dout):
 
     # gradient sources per block index: (dy_full tensor, ldf, foff, fmode), dy_pool tensor
     n = len(blocks)
-    src_full = [None] * n
-    src_pool = [None] * n
-    idx = {b.name: i for i, b in enumerate(blocks)}
-    head = n - 1
-    src_full[head] = (dout, blocks[head].cout, 0, 0)
-    n1 = len(dnn._blocks()[0])
-    i_pass = idx['passthrough']
+    src_full, src_pool = [None] * (n - 1) + [(dout, blocks[n - 1].cout, 0, 0)], [None] * n
+    routes, full, pooled = _routes([b.name for b in blocks], [b.pool for b in blocks], len(dnn._blocks()[0]), c_pt)
+    need_dx = bool(getattr(ctx, 'need_dx', False))
+    plans = _decide_bwd([_Geo(b.H, b.W, b.cin, b.cout, b.k, b.ldx, b.first, b.wino_v is not None, b.eff.padded,
+                              ctx.prepared[b.mod]['ud_ok'] if (not b.first and b.mod in ctx.prepared) else None, full[i], pooled[i]) for i, b in enumerate(blocks)], B, str(dev), need_dx)
     order = list(range(n - 1, -1, -1))
     main = torch.cuda.current_stream(dev)
     # (under capture only a StepPlan - which joins the side stream before it ends a graph segment, ctx.join - may fork: an unjoined stream fails the capture)
@@ -494,40 +553,26 @@ def _darknet_bwd(ctx, dout):
     # accumulation targets of the direct (split, atomically added) weight gradients and the zero-padded gradient of an unaligned head
     sums_arena = torch.empty(2 * sum(b.cout for b in blocks), dtype=torch.float64, device=dev)
     zero = [sums_arena]
-    if scope is not None:
-        bufs = (dev, scope)
-    else:
-        bufs = dnn.__dict__.setdefault('_train_bufs', (dev, {}))
-        if bufs[0] != dev:
-            bufs = dnn._train_bufs = (dev, {})
-
-    def persistent(tag, nel):
-        return cached_buf(bufs[1], tag, nel, dev)
-    wg = {}          # block index -> (accumulation target, it is the final gradient tensor, pre-zeroed)
-    dzs = {}
+    bufs = (dev, scope) if scope is not None else dnn.__dict__.setdefault('_train_bufs', (dev, {}))
+    if bufs[0] != dev:
+        bufs = dnn._train_bufs = (dev, {})
+    wg, dzs = {}, {}          # block index -> accumulation target of its weight gradient; -> zero-padded dz of an unaligned width
     for i in order:
-        blk = blocks[i]
-        e = blk.eff
+        blk, plan = blocks[i], plans[i]
         cop = (blk.cout + 3) // 4 * 4
         weight = blk.mod.conv.weight
         if cop != blk.cout:
             dzs[i] = _new(dev, B, blk.H, blk.W, cop)
             zero.append(dzs[i])
         if blk.first:
-            if blk.cin <= 3 and blk.cout <= 64:
-                t = dest(weight) if not e.padded else _new(dev, blk.cout, blk.cin, 3, 3)
-                wg[i] = (t, True, True)
-                zero.append(t)
-            continue
-        choice = _hip.wgrad_choice(B, blk.H, blk.W, blk.cin, blk.ldx, cop, cop, blk.k, blk.wino_v is not None, dev)
-        final = blk.k == 1 and cop == blk.cout and not e.padded        # [cout][1][cin] IS the state_dict layout: no unpack pass
-        if blk.k == 1:      # (never a persistent buffer: what this kernel writes is handed to autograd as it is, or as a prefix view)
-            t = dest(weight).view(-1) if final else _new(dev, cop * blk.cin)
+            if plan.final:
+                wg[i] = dest(weight) if not blk.eff.padded else _new(dev, blk.cout, blk.cin, 3, 3)
+        elif blk.k == 1:    # (never a persistent buffer: what this kernel writes is handed to autograd as it is, or as a prefix view)
+            wg[i] = dest(weight).view(-1) if plan.final else _new(dev, cop * blk.cin)
         else:               # packed [cout][tap][cin] staging of a 3x3 gradient, unpacked into the gradient tensor afterwards: reused every step
-            t = persistent((blk.name, 'dwp'), cop * blk.cin * blk.k * blk.k)
-        if choice == 0:
-            zero.append(t)
-        wg[i] = (t, final, choice == 0, choice)
+            wg[i] = cached_buf(bufs[1], (blk.name, 'dwp'), cop * blk.cin * blk.k * blk.k, dev)
+        if plan.zero:
+            zero.append(wg[i])
     _hip.multi([(_hip.MULTI_ZERO, t, None) for t in zero], st)
     sums_used = 0
 
@@ -539,7 +584,7 @@ def _darknet_bwd(ctx, dout):
             del held                 # (the main stream is behind the side stream's reads now: these blocks may be reused by what it launches next)
             ready(prm, g)
     for i in order:
-        blk = blocks[i]
+        blk, plan = blocks[i], plans[i]
         e = blk.eff
         L.y2_prof_set_tag(101 + i)                  # backward launches of block i: tag 101 + i
         h, w, cout, cin, k = blk.H, blk.W, blk.cout, blk.cin, blk.k
@@ -549,22 +594,10 @@ def _darknet_bwd(ctx, dout):
         # is handled in a zero-padded channel space here; unaligned widths elsewhere were padded by the forward (_pad_layout)
         cop = (cout + 3) // 4 * 4
         sf, sp = src_full[i], src_pool[i]
-        # first layer (model/yolo2.py:78-79: conv + pool, nothing below it needs a data gradient): its dz is consumed by the weight gradient
-        # alone, which forms it on the fly from (z, dy_pool) and the pass-1 sums - no dz tensor (1.4 GB at batch 64), no second pass
-        need_dx = bool(getattr(ctx, 'need_dx', False))
-        fuse0 = (FUSE_CONV0 and blk.first and i in wg and sf is None and sp is not None and not (h & 1) and not (w & 15)
-                 and B * h * w * cout * 4 < 0xffff0000 and not need_dx)
-        # A deep 3x3 block whose weight gradient AND data gradient both run the 4x4-tile Winograd forms reads dz only through their two transforms:
-        # y2_bn_act_bwd_wino6 writes those instead of dz (pass 2 + wino6_in x 2 in one kernel, bit-identical operands; csrc/train.hip).  Known in advance
-        # from the algorithm table (nothing is measured here: an unknown problem takes the three-kernel form and gets measured there).
-        ready_ops = ctx.prepared.get(blk.mod) if not blk.first else None
-        fused6 = None
-        if (FUSE_WINO6 and k == 3 and not blk.first and ready_ops is not None and sp is None and sf is not None and sf[3] == 0 and cop == cout and not e.padded
-                and i in wg and wg[i][3] == 2 and DEBUG_TAP is None and not _hip.DETERMINISTIC and not _hip.split_mode()):
-            hit = _conv(L, st, None, ready_ops['wd'], None, B, h, w, cop, cop, cin, k, cin, u=ready_ops['ud'], grad=True, u_eligible=ready_ops['ud_ok'], u6=ready_ops.get('u6d'), peek=True, dev=dev)
-            if hit is not None and hit[0] == 6:
-                T6 = int(L.y2_wino6_tiles(B, h, w))
-                fused6 = (_new(dev, 36 * T6 * cout), _new(dev, 36 * T6 * cout))
+        fuse0, fused6 = plan.fuse0, None
+        if plan.fused6:          # (its two transformed forms of dz: the data gradient's input, the weight gradient's)
+            T6 = int(L.y2_wino6_tiles(B, h, w))
+            fused6 = (_new(dev, 36 * T6 * cout), _new(dev, 36 * T6 * cout))
         dz = None if (fuse0 or fused6) else (dzs[i] if i in dzs else _new(dev, B, h, w, cop))
         if DEBUG_TAP is not None:
             DEBUG_TAP(blk.name + ':in', blk.z, blk.shift, sf, sp)
@@ -601,16 +634,14 @@ def _darknet_bwd(ctx, dout):
             return dw
 
         def weight_grad(st_w):
-            if i in wg and blk.first and fuse0:
-                dw0 = wg[i][0]
+            if blk.first and fuse0:
                 _hip.check(L.y2_conv0_wgrad_fused(_hip.ptr(ctx.x), _hip.ptr(blk.z), _hip.ptr(blk.scale), _hip.ptr(blk.shift), _hip.ptr(blk.mean), _hip.ptr(blk.invstd),
-                                                  _hip.ptr(e.gamma) if blk.has_bn else None, blk.slope, _hip.ptr(sp), cout, _hip.ptr(sums), _hip.ptr(dw0),
+                                                  _hip.ptr(e.gamma) if blk.has_bn else None, blk.slope, _hip.ptr(sp), cout, _hip.ptr(sums), _hip.ptr(wg[i]),
                                                   B, h, w, cin, cout, cout, (2 if ctx.frozen else 1) if blk.has_bn else 0, st_w), 'y2_conv0_wgrad_fused')
-                return real(dw0)
-            if i in wg and blk.first:
-                dw0 = wg[i][0]
-                _hip.check(L.y2_conv0_wgrad(_hip.ptr(ctx.x), _hip.ptr(dz), _hip.ptr(dw0), B, h, w, cin, cout, cop, st_w), 'y2_conv0_wgrad')
-                return real(dw0)
+                return real(wg[i])
+            if blk.first and plan.final:
+                _hip.check(L.y2_conv0_wgrad(_hip.ptr(ctx.x), _hip.ptr(dz), _hip.ptr(wg[i]), B, h, w, cin, cout, cop, st_w), 'y2_conv0_wgrad')
+                return real(wg[i])
             if blk.first:
                 x4 = torch.zeros(B, h, w, 4, dtype=torch.float32, device=dev)
                 x4[..., :cin] = ctx.x.permute(0, 2, 3, 1)          # layout conversion only (NCHW plugin input -> NHWC, 4th channel zero)
@@ -619,22 +650,15 @@ def _darknet_bwd(ctx, dout):
                 dw4 = _new(dev, cop, 4, k, k)
                 _hip.check(L.y2_unpack_weight_grad(_hip.ptr(dwp), _hip.ptr(dw4), cop, 4, k, st_w), 'y2_unpack_weight_grad')
                 return dw4[:e.cout_r, :cin].contiguous()
-            tgt, final, zeroed = wg[i][:3]
-            if not zeroed and wg[i][3] is None:
-                # The algorithm of this shape was unmeasured when the step's zero fill was planned, so the target was left out of it - and an earlier
-                # layer of the SAME shape may have measured "direct" (which accumulates) since.  conv_wgrad's own fill runs on torch's current stream,
-                # the main stream here, unordered against the accumulating kernel on the side stream (seen as a garbage gradient of the second layer
-                # of a shape in the first backward of a process): fill on the stream the weight gradient runs on.
+            tgt = wg[i]
+            if plan.wgrad is None:      # unknown when the pass was planned: whatever it resolves to below (measured; "direct" accumulates) finds a zeroed target
                 _hip.multi([(_hip.MULTI_ZERO, tgt, None)], st_w)
-                zeroed = True
             dw = None
             if k == 3:
                 dw = dest(weight) if (cop == cout and not e.padded) else _new(dev, cop, cin, k, k)
-            if fused6:
-                got = _hip.conv_wgrad(blk.x, fused6[1], B, h, w, cin, blk.ldx, cop, cop, k, v=blk.wino_v, out=tgt, zeroed=zeroed, native=dw, dz_pre=True)
-            else:
-                got = _hip.conv_wgrad(blk.x, dz, B, h, w, cin, blk.ldx, cop, cop, k, v=blk.wino_v, out=tgt, zeroed=zeroed, native=dw)     # direct or Winograd, by measurement
-            if final:
+            got = _hip.conv_wgrad(blk.x, fused6[1] if fused6 else dz, B, h, w, cin, blk.ldx, cop, cop, k, v=blk.wino_v, out=tgt, zeroed=plan.zero or plan.wgrad is None,
+                                  native=dw, dz_pre=bool(fused6), choice=plan.wgrad)
+            if plan.final:
                 return tgt.view(cout, cin, 1, 1)
             if k == 1:
                 return real(tgt.view(cop, cin, 1, 1))
@@ -642,7 +666,7 @@ def _darknet_bwd(ctx, dout):
                 _hip.check(L.y2_unpack_weight_grad(_hip.ptr(tgt), _hip.ptr(dw), cop, cin, k, st_w), 'y2_unpack_weight_grad')
             return real(dw)
 
-        if side is not None and not e.padded and (not blk.first or i in wg):       # (the rare paths above mix torch-native kernels in: not forked)
+        if side is not None and not e.padded and (not blk.first or plan.final):       # (the rare paths above mix torch-native kernels in: not forked)
             ev = torch.cuda.Event()
             ev.record(main)                           # dz (and everything before it) is complete on the main stream
             with _hip.launch_on(side):
@@ -676,15 +700,13 @@ def _darknet_bwd(ctx, dout):
             # data gradient -> the producer's gradient source
             dx = _new(dev, B, h, w, cin)
             ready_ops = ctx.prepared.get(blk.mod)
-            if fused6:
-                _conv(L, st, None, ready_ops['wd'], dx, B, h, w, cop, cop, cin, k, cin, u=ready_ops['ud'], grad=True,
-                      note=lambda kind, m=blk.mod: ctx.used.add((m, 'wd' if kind == 'w' else 'u6d' if kind == '6' else 'ud')), u_eligible=ready_ops['ud_ok'], u6=ready_ops.get('u6d'), pre=fused6[0])
-            elif ready_ops is not None:        # rotated / in-out-swapped operands prepared with the forward's (same parameter version)
+            if ready_ops is not None:          # rotated / in-out-swapped operands prepared with the forward's (same parameter version)
                 # (the fp16 split mode is for activations: its fixed operand scales assume O(1) values, and gradients are 1e-5 and smaller -
                 # their fp16 planes would be subnormal; data gradients stay on the fp32 / bf16-split algorithms)
                 dg_split = ready_ops['uds'] if _hip.split_mode() == 'bf16' else None
                 _conv(L, st, dz, ready_ops['wd'], dx, B, h, w, cop, cop, cin, k, cin, u=ready_ops['ud'], us=dg_split, us_plane=ready_ops['plane'], grad=True,
-                      note=lambda kind, m=blk.mod: ctx.used.add((m, 'wd' if kind == 'w' else 'u6d' if kind == '6' else 'ud')), u_eligible=ready_ops['ud_ok'], u6=ready_ops.get('u6d'))
+                      note=lambda kind, m=blk.mod: ctx.used.add((m, 'wd' if kind == 'w' else 'u6d' if kind == '6' else 'ud')), u_eligible=ready_ops['ud_ok'], u6=ready_ops.get('u6d'),
+                      choice=plan.fused6, pre=fused6[0] if fused6 else None, problem=plan.problem)
             else:
                 wsrc = e.w
                 if cop != cout:
@@ -698,22 +720,11 @@ def _darknet_bwd(ctx, dout):
                 _conv(L, st, dz, wd, dx, B, h, w, cop, cop, cin, k, cin)
             if DEBUG_TAP is not None and dz is not None:
                 DEBUG_TAP(blk.name, dz, dx, None, None)
-            # route dx
-            if blk.name == 'layers3.0':
-                dcat = dx                                           # [B,h,w,4*c_pt + c_l2]
-                src_full[i_pass] = (dcat, dcat.shape[-1], 0, 1)     # reorg'ed channels first
-                src_full[idx[dnn._blocks()[1][-1][0]]] = (dcat, dcat.shape[-1], 4 * c_pt, 0)
-            elif blk.name == 'passthrough':
-                j = n1 - 1
-                src_full[j] = (dx, cin, 0, 0)
-            elif i == n1 + 1 and blk.name.startswith('layers2.'):   # first conv of layers2: its input is the pooled layers1[-1]
-                src_pool[n1 - 1] = dx
-            else:
-                prod = i - 1
-                if blocks[prod].pool:
-                    src_pool[prod] = dx
+            for j, to_pool, off, mode in routes[i]:          # dx is the consumer's gradient source
+                if to_pool:
+                    src_pool[j] = dx
                 else:
-                    src_full[prod] = (dx, cin, 0, 0)
+                    src_full[j] = (dx, cin, off, mode)
         blk.z = None   # free as we go
     sink.hand_affine(sums_arena, affine_grads, st)          # fp64 sums -> fp32, one launch
     flush_weight_grads()

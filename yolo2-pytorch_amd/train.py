@@ -347,7 +347,8 @@ class DataParallelRCCL(nn.Module):
             assert bi == self._next, (bi, self._next)
             if bi == 0:
                 # the same point of the collective sequence as _start() on the hook path - behind the loss's positive-count all-reduce, in front of bucket 0 - so
-                # a rank replaying graph segments and a rank on the hook path meet the tune broadcast at the same place
+                # a rank replaying graph segments and a rank on the hook path meet the tune broadcast at the same place.  On an eager pass this is the middle of
+                # the backward: harmless, the pass in flight took its decisions before its first launch (train_graph._decide_bwd), the table adopted here serves the next
                 self._count_step()
             flat = self._flat[bi]
             flat[flat.numel() - len(self._buckets[bi]):].fill_(1.0)
