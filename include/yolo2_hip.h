@@ -320,6 +320,33 @@ int y2_eval_match(const float* det_min, const float* det_max, const long long* d
 int y2_collate_images(const uint8_t* src, const int64_t* offset, const int32_t* geom, const float* lut,
                       int32_t B, int32_t H, int32_t W, int32_t flags, float* out, y2_stream_t stream);
 
+/* The rotation of the data pipeline (transform/augmentation.py:28-75: cv2.warpAffine(image, M, dsize, INTER_LINEAR, BORDER_CONSTANT, fill) with the
+ * matrix of cv2.getRotationMatrix2D on a grown canvas) for a ragged batch of uint8 images in ONE launch: the stage in front of y2_collate_images.
+ * src / src_offset: as y2_collate_images.  src_geom [B][4] int32: {row_stride_bytes, src_h, src_w, flip}; with flip set, source column x is read at
+ * src_w - 1 - x (a flip recorded BEFORE the rotation).  inv [B][6] double: A, the INVERSE map, destination (x, y) -> source
+ * (A0 x + A1 y + A2, A3 x + A4 y + A5).  dst / dst_offset / dst_geom [B][8]: the destination images, in the layout of the tables y2_collate_images
+ * reads next - columns 0-2 {row_stride_bytes, dst_h, dst_w} are read here, the rest is ignored.  Bytes of a destination row beyond 3 * dst_w are
+ * not written.  max_h, max_w: the largest dst_h and dst_w of the batch (the grid; an image larger than that is cut there).
+ * fill: the level outside the source, 0xC2C1C0 = one byte per source channel (channel c: fill >> 8c; the reference passes 0).
+ * Resampling - cv2.warpAffine for 8-bit 3-channel images, INTER_LINEAR, BORDER_CONSTANT, restated.  For destination pixel (x, y), every double
+ * operation rounded separately, lrint = round to nearest even:
+ *   adelta = lrint((A0 * x) * 1024), bdelta = lrint((A3 * x) * 1024); X0 = lrint((A1 * y + A2) * 1024) + 16, Y0 = lrint((A4 * y + A5) * 1024) + 16;
+ *   X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5 (arithmetic shifts); sx = X >> 5, ax = X & 31, sy = Y >> 5, ay = Y & 31, sx and sy saturated to
+ *   [-32768, 32767].  Taps (sy, sx), (sy, sx + 1), (sy + 1, sx), (sy + 1, sx + 1); a tap outside [0, src_h) x [0, src_w) reads the fill level; with
+ *   flip an inside tap reads source column src_w - 1 - sx.  Per channel
+ *   level = (p00 (32 - ax)(32 - ay) + p01 ax (32 - ay) + p10 (32 - ax) ay + p11 ax ay + 512) >> 10
+ * (OpenCV's 15-bit table form (sum p w + 2^14) >> 15: its bilinear weights are exactly 32 x these products, so the table's sum correction never
+ * fires).  Integer after the lrints: bit-identical on device and host.  The identity map is an exact copy.
+ * All dimensions in [1, Y2_WARP_MAX_DIM]; |A0|, |A1|, |A3|, |A4| <= 4 and |A2|, |A5| <= 2^19, so every sum above fits int32.  The tables are DEVICE
+ * memory: the device entry point cannot check them (utils.data.to_device and the host function do); it rounds through a saturating clamp, forms
+ * the sums in 64 bits and reads no tap outside the image the table names.  B == 0: nothing is launched.  12-byte stores (4 pixels) where
+ * dst + dst_offset[b] and the row stride are multiples of 4, byte stores otherwise and for the last dst_w % 4 pixels of a row.  Never allocates,
+ * never synchronises. */
+#define Y2_WARP_MAX_DIM 16384
+int y2_warp_affine_images(const uint8_t* src, const int64_t* src_offset, const int32_t* src_geom, const double* inv,
+                          uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
+                          int32_t B, int32_t max_h, int32_t max_w, int32_t fill, y2_stream_t stream);
+
 /* batch_iou_matrix: [Bt,N1,2]x2, [Bt,N2,2]x2 -> out [Bt,N1,N2]; iou_matrix is Bt = 1.  min_union = eps32.
  * mode 0: IoU (utils/iou/torch.py:47-61, 139-153);  mode 1: intersection area only (:24-44, 116-136). */
 int y2_iou_matrix(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
@@ -359,6 +386,12 @@ int y2_eval_match_host(const float* det_min, const float* det_max, const long lo
  * (offset >= 0, row_stride_bytes >= 3 * src_w, the window inside the image, flip 0 or 1): Y2_EINVAL, nothing is written. */
 int y2_collate_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const float* lut,
                            int32_t B, int32_t H, int32_t W, int32_t flags, float* out);
+/* y2_warp_affine_images on host memory: the same arithmetic, bit-identical output.  The tables are checked first (offsets >= 0, source dimensions
+ * in [1, Y2_WARP_MAX_DIM], dst_h <= max_h, dst_w <= max_w, row strides >= 3 * width, flip 0 or 1, the ranges of A above): Y2_EINVAL, nothing is
+ * written. */
+int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src_offset, const int32_t* src_geom, const double* inv,
+                               uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
+                               int32_t B, int32_t max_h, int32_t max_w, int32_t fill);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic mode (opt-in, process-global; one process per GPU, one stream).  By default the split-K weight gradient, the

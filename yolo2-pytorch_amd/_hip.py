@@ -58,6 +58,7 @@ MULTI_ZERO, MULTI_F64_TO_F32, MULTI_COPY = 0, 1, 2
 
 EVAL_MATCH_MAX_G = 1024      # Y2_EVAL_MATCH_MAX_G (include/yolo2_hip.h)
 COLLATE_MAX_W = 4096         # Y2_COLLATE_MAX_W
+WARP_MAX_DIM = 16384         # Y2_WARP_MAX_DIM
 
 SIGNATURES = {
     'y2_abi_version': [],
@@ -134,6 +135,8 @@ SIGNATURES = {
     'y2_eval_match_host': [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
     'y2_collate_images': [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     'y2_collate_images_host': [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p],
+    'y2_warp_affine_images': [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p],
+    'y2_warp_affine_images_host': [c_void_p] * 7 + [c_int, c_int, c_int, c_int],
     'y2_set_deterministic': [c_int, c_void_p, ctypes.c_longlong],
     'y2_get_deterministic': [],
     'y2_colstats_det': [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],

@@ -1,5 +1,5 @@
 // host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
-// y2_eval_match_host, y2_collate_images_host).
+// y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -46,6 +46,10 @@ inline void collate_axis(int i, int s, int d, bool edge, int& k, int& c0, int& c
 }
 
 inline int collate_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// warp.hip: wp_round, wp_clamp16 (rint rounds to nearest even in the default rounding mode, which nothing here changes)
+inline long long warp_round(double v) { return (long long)(int)fmin(fmax(rint(v), -2147483648.0), 2147483647.0); }
+inline int warp_clamp16(long long v) { return (int)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
 
 }  // namespace
 
@@ -225,6 +229,54 @@ extern "C" int y2_collate_images_host(const uint8_t* src, const int64_t* offset,
                         level = collate_clamp((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2, 0, 255);
                     }
                     row[x] = lut[c * 256 + level];
+                }
+            }
+        }
+    }
+    return Y2_OK;
+}
+
+// y2_warp_affine_images on host memory (warp.hip: warp_affine_images_kernel, serially).  The tables are readable here, so they are checked before
+// anything is written.
+extern "C" int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src_offset, const int32_t* src_geom, const double* inv,
+                                          uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
+                                          int32_t B, int32_t max_h, int32_t max_w, int32_t fill) {
+    if (B < 0 || max_h < 1 || max_h > Y2_WARP_MAX_DIM || max_w < 1 || max_w > Y2_WARP_MAX_DIM || (fill & ~0xffffff)) return Y2_EINVAL;
+    if (B == 0) return Y2_OK;
+    if (B > 65535) return Y2_ENOSUP;
+    if (!src || !src_offset || !src_geom || !inv || !dst || !dst_offset || !dst_geom) return Y2_EINVAL;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* sg = src_geom + 4 * (size_t)b;
+        const int32_t* dg = dst_geom + 8 * (size_t)b;
+        const double* A = inv + 6 * (size_t)b;
+        if (src_offset[b] < 0 || sg[1] < 1 || sg[1] > Y2_WARP_MAX_DIM || sg[2] < 1 || sg[2] > Y2_WARP_MAX_DIM || sg[0] < 3 * sg[2] || (sg[3] != 0 && sg[3] != 1))
+            return Y2_EINVAL;
+        if (dst_offset[b] < 0 || dg[1] < 1 || dg[1] > max_h || dg[2] < 1 || dg[2] > max_w || dg[0] < 3 * dg[2]) return Y2_EINVAL;
+        // (negated comparisons: a NaN is refused)
+        if (!(fabs(A[0]) <= 4.0 && fabs(A[1]) <= 4.0 && fabs(A[3]) <= 4.0 && fabs(A[4]) <= 4.0 && fabs(A[2]) <= 524288.0 && fabs(A[5]) <= 524288.0))
+            return Y2_EINVAL;
+    }
+    for (int b = 0; b < B; ++b) {
+        const int32_t* sg = src_geom + 4 * (size_t)b;
+        const int32_t* dg = dst_geom + 8 * (size_t)b;
+        const int stride = sg[0], src_h = sg[1], src_w = sg[2], flip = sg[3], dstride = dg[0], dst_h = dg[1], dst_w = dg[2];
+        const double* A = inv + 6 * (size_t)b;
+        const uint8_t* img = src + src_offset[b];
+        for (int y = 0; y < dst_h; ++y) {
+            const long long X0 = warp_round((A[1] * (double)y + A[2]) * 1024.0) + 16, Y0 = warp_round((A[4] * (double)y + A[5]) * 1024.0) + 16;
+            uint8_t* o = dst + dst_offset[b] + (long long)y * dstride;
+            for (int x = 0; x < dst_w; ++x) {
+                const long long X = (X0 + warp_round((A[0] * (double)x) * 1024.0)) >> 5, Y = (Y0 + warp_round((A[3] * (double)x) * 1024.0)) >> 5;
+                const int sx = warp_clamp16(X >> 5), sy = warp_clamp16(Y >> 5), ax = (int)(X & 31), ay = (int)(Y & 31);
+                const int w00 = (32 - ax) * (32 - ay), w01 = ax * (32 - ay), w10 = (32 - ax) * ay, w11 = ax * ay;
+                const bool x0 = sx >= 0 && sx < src_w, x1 = sx + 1 >= 0 && sx + 1 < src_w, y0 = sy >= 0 && sy < src_h, y1 = sy + 1 >= 0 && sy + 1 < src_h;
+                const long long c0 = 3LL * (flip ? src_w - 1 - sx : sx), c1 = 3LL * (flip ? src_w - 2 - sx : sx + 1);
+                const long long r0 = (long long)sy * stride, r1 = r0 + stride;          // (offsets, not pointers: a tap outside the image is never formed)
+                for (int c = 0; c < 3; ++c) {
+                    const int f = (fill >> (8 * c)) & 255;
+                    const int p00 = (y0 && x0) ? (int)img[r0 + c0 + c] : f, p01 = (y0 && x1) ? (int)img[r0 + c1 + c] : f;
+                    const int p10 = (y1 && x0) ? (int)img[r1 + c0 + c] : f, p11 = (y1 && x1) ? (int)img[r1 + c1 + c] : f;
+                    o[3 * x + c] = (uint8_t)((p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 512) >> 10);
                 }
             }
         }

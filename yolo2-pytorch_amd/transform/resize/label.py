@@ -2,17 +2,18 @@
 (transform/resize/label.py), for the device collate step.
 
 Each one leaves `data['image']` - the uint8 array as it was read - alone and records which part of it the sample shows, `data['window'] =
-(y0, x0, h, w)` in the frame after the optional flip (`data['flip']`), for y2_collate_images to resample.  The labels get the arithmetic of the
+(y0, x0, h, w)` in the frame after the optional rotation (`data['rotate']`) and flip (`data['flip']`), for y2_collate_images to resample.  The labels get the arithmetic of the
 reference in float32, operation for operation, and the random numbers are drawn as the reference draws them (tests/golden/collate.npz pins both).
 A sample is resized ONCE: after it the labels are in output coordinates, so a second resize transform on the same sample raises."""
 import numpy as np
+
+from transform import frame_size
 
 
 def _source_size(data, who):
     if 'window' in data:
         raise ValueError('%s: the sample already carries a window - one resize transform per sample' % who)
-    height, width = data['image'].shape[:2]
-    return height, width
+    return frame_size(data)
 
 
 def _to_output(data, window, height, width):

@@ -7,6 +7,11 @@ zero rows and packs the untouched uint8 images into one byte buffer with an offs
 Normalize as a table) writes `batch['tensor']`, the fp32 [B,3,H,W] input of the network.  On 'cpu' it runs y2_collate_images_host, the
 bit-identical host function.
 
+A batch in which a sample went through transform.augmentation.RandomRotate takes one launch more: `Collate` adds the tables of
+y2_warp_affine_images (`src_offset`, `src_geom`, `warp`: the inverse matrices, `rot_bytes`, `rot_size`), `offset` / `geom` then describe the ROTATED
+images inside an intermediate device buffer, and `to_device` launches the warp in front of the collate kernel.  A batch without a rotated sample
+is untouched by all this: the same keys, the same bytes, one launch.
+
 What ships to the device is the source pixels as cv2.imread returned them - a quarter to a third of the bytes of the finished fp32 tensor."""
 import os
 import pickle
@@ -16,6 +21,7 @@ import numpy as np
 import torch
 
 import _hip
+from transform import frame_size
 
 LABELS = 'yx_min, yx_max, cls, difficult'.split(', ')
 
@@ -41,6 +47,41 @@ def check_geometry(offset, geom, nbytes):
     if bad.any():
         b = int(np.argmax(bad))
         raise ValueError('collate: image %d: window or image outside its buffer (offset %d of %d bytes, geom %s)' % (b, offset[b], nbytes, geom[b].tolist()))
+
+
+def invert_affine(matrix):
+    """The inverse of a 2x3 affine map as 6 float64 (A0 .. A5: destination -> source), in the operation order of cv2.warpAffine's own inversion."""
+    M0, M1, M2, M3, M4, M5 = (float(v) for v in np.asarray(matrix, np.float64).reshape(6))
+    D = M0 * M4 - M1 * M3
+    D = 1.0 / D if D != 0 else 0.0
+    A0, A4, A1, A3 = M4 * D, M0 * D, -M1 * D, -M3 * D
+    return np.array([A0, A1, -A0 * M2 - A1 * M5, A3, A4, -A3 * M2 - A4 * M5], np.float64)
+
+
+def check_warp(src_offset, src_geom, warp, src_bytes, offset, geom, rot_bytes):
+    """The tables of y2_warp_affine_images against the two byte buffers (host arrays): every source inside `src_bytes`, every destination inside
+    `rot_bytes`, dimensions and matrix entries in the ranges of include/yolo2_hip.h."""
+    src_offset, src_geom, offset, geom = (np.asarray(a, np.int64) for a in (src_offset, src_geom, offset, geom))
+    warp = np.asarray(warp, np.float64)
+    B = len(geom)
+    if src_geom.shape != (B, 4) or src_offset.shape != (B,) or warp.shape != (B, 6) or geom.shape != (B, 8) or offset.shape != (B,):
+        raise ValueError('warp: src_offset must be [B], src_geom [B, 4], warp [B, 6] beside offset [B] and geom [B, 8]')
+    stride, src_h, src_w, flip = src_geom.T
+    dstride, dst_h, dst_w = geom.T[:3]
+    limit = _hip.WARP_MAX_DIM
+    with np.errstate(invalid='ignore'):
+        in_range = (np.abs(warp[:, [0, 1, 3, 4]]) <= 4).all(1) & (np.abs(warp[:, [2, 5]]) <= 2 ** 19).all(1)          # (a NaN is out of range)
+    bad = ((src_offset < 0) | (src_h < 1) | (src_h > limit) | (src_w < 1) | (src_w > limit) | (stride < 3 * src_w) | ((flip != 0) & (flip != 1))
+           | (src_offset + (src_h - 1) * stride + 3 * src_w > src_bytes)
+           | (offset < 0) | (dst_h < 1) | (dst_h > limit) | (dst_w < 1) | (dst_w > limit) | (dstride < 3 * dst_w)
+           | (offset + (dst_h - 1) * dstride + 3 * dst_w > rot_bytes) | ~in_range)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError('warp: image %d: source or rotated image outside its buffer, or matrix out of range (src_offset %d of %d bytes, src_geom %s, '
+                         'offset %d of %d bytes, geom %s, warp %s)' % (b, src_offset[b], src_bytes, src_geom[b].tolist(), offset[b], rot_bytes, geom[b, :3].tolist(), warp[b].tolist()))
+
+
+ROT_ROW_ALIGN, ROT_IMAGE_ALIGN = 16, 64      # the layout of the rotated images is Collate's: rows and images start where the warp kernel's 12-byte stores are aligned
 
 
 class Collate(object):
@@ -102,9 +143,29 @@ class Collate(object):
         raw = np.empty(pos, np.uint8)
         for b, data in enumerate(samples):
             raw[offset[b]:offset[b] + data['image'].size] = data['image'].reshape(-1)
+        extra = {}
+        if any('rotate' in data for data in samples):
+            # every sample goes through the warp stage (an un-rotated one with the identity, an exact copy): what was packed above is its source, and
+            # offset / geom move on to the rotated images inside the intermediate buffer
+            src_offset, src_geom = offset, np.zeros((len(samples), 4), np.int32)
+            offset, warp = np.zeros(len(samples), np.int64), np.zeros((len(samples), 6), np.float64)
+            pos = 0
+            for b, data in enumerate(samples):
+                rotate = data.get('rotate')
+                h, w = frame_size(data)
+                stride = -(-3 * w // ROT_ROW_ALIGN) * ROT_ROW_ALIGN
+                src_geom[b] = tuple(geom[b, :3]) + (int(rotate['flip']) if rotate else 0,)
+                warp[b] = invert_affine(rotate['matrix']) if rotate else (1, 0, 0, 0, 1, 0)
+                offset[b] = pos
+                geom[b, :3] = (stride, h, w)
+                pos += -(-h * stride // ROT_IMAGE_ALIGN) * ROT_IMAGE_ALIGN
+            check_warp(src_offset, src_geom, warp, raw.size, offset, geom, pos)
+            extra = dict(src_offset=torch.from_numpy(src_offset), src_geom=torch.from_numpy(src_geom), warp=torch.from_numpy(warp), rot_bytes=pos,
+                       rot_size=(int(geom[:, 1].max()), int(geom[:, 2].max())))
         check_geometry(offset, geom, pos)
         out.update(raw=torch.from_numpy(raw), offset=torch.from_numpy(offset), geom=torch.from_numpy(geom), size=(height, width),
                    swap_rb=self.swap_rb, normalize=self.normalize)
+        out.update(extra)
         return out
 
 
@@ -129,13 +190,17 @@ def level_table(normalize, device):
     return lut
 
 
-def to_device(batch, device=None, out=None):
+def to_device(batch, device=None, out=None, rot=None):
     """The main-process half of the collate step: a copy of `batch` (the dict of Collate) with every tensor on `device` - at most one copy each,
     non_blocking from pinned memory, no synchronisation once level_table() has met this (normalize, device) - and `tensor` [B,3,H,W] fp32 written by one y2_collate_images launch on the current
     stream (device 'cpu': y2_collate_images_host).  device=None: where `raw` is when that is a GPU, else the current GPU, else the CPU.
     `out`: the destination (e.g. the static input buffer of a captured graph) instead of a fresh tensor.  `batch['lut']` ([3,256] fp32), when
     present, replaces the ToTensor + Normalize table (any per-level map, e.g. a gamma curve).  The tables are checked here while they are host
-    memory; tables that arrive on the device are the caller's."""
+    memory; tables that arrive on the device are the caller's.
+    A batch with `warp` (a sample was rotated) takes TWO launches: y2_warp_affine_images writes every rotated uint8 image into an intermediate buffer
+    of `batch['rot_bytes']` bytes - `rot`, a contiguous uint8 tensor of at least that size on `device` (a captured graph's static buffer), or a fresh
+    torch.empty - and y2_collate_images reads that buffer instead of `raw`.  The result carries it as `rot`.  `batch['fill']` (0xC2C1C0, one byte per
+    source channel; default 0, what the reference passes) is the level outside the source.  Without `warp`, `rot` is not touched."""
     raw = batch['raw']
     if device is None:
         device = raw.device if raw.is_cuda else torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
@@ -143,8 +208,12 @@ def to_device(batch, device=None, out=None):
     if device.type == 'cuda' and device.index is None:
         device = torch.device('cuda', torch.cuda.current_device())
     H, W = (int(v) for v in batch['size'])
+    warped = 'warp' in batch
+    pixels = int(batch['rot_bytes']) if warped else raw.numel()          # the buffer that offset / geom index
     if not batch['geom'].is_cuda and not batch['offset'].is_cuda:
-        check_geometry(batch['offset'].numpy(), batch['geom'].numpy(), raw.numel())
+        check_geometry(batch['offset'].numpy(), batch['geom'].numpy(), pixels)
+        if warped and not any(batch[k].is_cuda for k in ('src_offset', 'src_geom', 'warp')):
+            check_warp(batch['src_offset'].numpy(), batch['src_geom'].numpy(), batch['warp'].numpy(), raw.numel(), batch['offset'].numpy(), batch['geom'].numpy(), pixels)
     res = {k: (v.to(device, non_blocking=v.is_pinned()) if torch.is_tensor(v) else v) for k, v in batch.items()}
     raw, offset, geom = res['raw'], res['offset'], res['geom']
     B = geom.size(0)
@@ -162,11 +231,31 @@ def to_device(batch, device=None, out=None):
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous() or out.device != device:
         raise ValueError('to_device: out must be a contiguous fp32 [%d, 3, %d, %d] tensor on %s' % (B, H, W, device))
+    warp_args = None
+    if warped:
+        src_offset, src_geom, inv = res['src_offset'].contiguous(), res['src_geom'].contiguous(), res['warp'].contiguous()
+        if (src_offset.dtype != torch.int64 or src_geom.dtype != torch.int32 or inv.dtype != torch.float64 or tuple(src_geom.shape) != (B, 4)
+                or tuple(inv.shape) != (B, 6) or src_offset.numel() != B):
+            raise ValueError('to_device: src_offset must be int64 [B], src_geom int32 [B, 4], warp float64 [B, 6]')
+        max_h, max_w = (int(v) for v in batch['rot_size'])
+        if not (0 < max_h <= _hip.WARP_MAX_DIM and 0 < max_w <= _hip.WARP_MAX_DIM):
+            raise ValueError('to_device: rot_size %dx%d (a rotated image is limited to %d rows and columns)' % (max_h, max_w, _hip.WARP_MAX_DIM))
+        if rot is None:
+            rot = torch.empty(pixels, dtype=torch.uint8, device=device)
+        elif rot.dtype != torch.uint8 or rot.numel() < pixels or not rot.is_contiguous() or rot.device != device:
+            raise ValueError('to_device: rot must be a contiguous uint8 tensor of at least %d bytes on %s' % (pixels, device))
+        warp_args = (raw.data_ptr(), src_offset.data_ptr(), src_geom.data_ptr(), inv.data_ptr(), rot.data_ptr(), offset.data_ptr(), geom.data_ptr(),
+                     B, max_h, max_w, int(batch.get('fill', 0)))
+        raw = res['rot'] = rot
     args = (raw.data_ptr(), offset.data_ptr(), geom.data_ptr(), lut.data_ptr(), B, H, W, 1 if batch.get('swap_rb', True) else 0, out.data_ptr())
     if device.type == 'cuda':
         with torch.cuda.device(device):
+            if warped:
+                _hip.check(_hip.lib().y2_warp_affine_images(*warp_args, _hip.stream()), 'y2_warp_affine_images')
             _hip.check(_hip.lib().y2_collate_images(*args, _hip.stream()), 'y2_collate_images')
     else:
+        if warped:
+            _hip.check(_hip.lib().y2_warp_affine_images_host(*warp_args), 'y2_warp_affine_images_host')
         _hip.check(_hip.lib().y2_collate_images_host(*args), 'y2_collate_images_host')
     res['tensor'] = out
     return res
