@@ -347,6 +347,42 @@ int y2_warp_affine_images(const uint8_t* src, const int64_t* src_offset, const i
                           uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
                           int32_t B, int32_t max_h, int32_t max_w, int32_t fill, y2_stream_t stream);
 
+/* The collate step WITH the colour jitter of the data pipeline (utils/data.py:120-121: resize, then transform_image - transform/image.py: RandomBlur,
+ * BGR2HSV, RandomHue / RandomSaturation / RandomBrightness, HSV2RGB, RandomGamma - then ToTensor, Normalize) for a ragged batch in ONE launch, in
+ * place of y2_collate_images.  src / offset / geom, B, H, W, flags and out mean exactly what they mean there (so it reads the output of
+ * y2_warp_affine_images unchanged).  jitter [B][4] int32: {kx, ky, hsv (0 / 1), 0}.  hsv_tab [B][3][256] uint8: the image's H, S and V tables (may be
+ * NULL when no image sets hsv).  lut [B][3][256] fp32: PER IMAGE, indexed by output plane (gamma, ToTensor and Normalize composed by the host).
+ * Per output image:
+ * (a) Resize: the BGR level of every pixel of the H x W image by the resampling of y2_collate_images above (window, flip, taps, 11-bit coefficients,
+ *     the 2x2 box mean at exactly 2:1).
+ * (b) Blur - cv2.blur(image, (kx, ky)), restated: a normalised box filter per channel, anchor (kx / 2, ky / 2) in integer division, so the window of
+ *     column x is x - kx / 2 .. x - kx / 2 + kx - 1 (rows alike); BORDER_REFLECT_101 on the RESIZED image's coordinates, borderInterpolate's loop:
+ *     p < 0 -> -p, p >= n -> 2 n - 2 - p, repeated until 0 <= p < n, and n == 1 -> 0.  s = the integer sum of the kx * ky window;
+ *     level = clamp(rint((double)s * (1.0 / (double)(kx * ky))), 0, 255), rint = round half to even (the ColumnSum<int, uchar> path).
+ *     1 <= kx, ky <= Y2_JITTER_MAX_BLUR; kx == ky == 1 gives the level back untouched.
+ * (c) Colour.  hsv == 0: output plane c takes source channel 2 - c with flags bit 0 (BGR2RGB), else channel c.  hsv == 1: 8-bit COLOR_BGR2HSV, the
+ *     three tables applied to H, S and V, 8-bit COLOR_HSV2RGB; the planes are R, G, B whatever flags says.
+ *     BGR2HSV, restated (integers, arithmetic right shifts, cvRound = round half to even): sdiv[i] = cvRound((255 << 12) / (1.0 * i)),
+ *     hdiv[i] = cvRound((180 << 12) / (6.0 * i)), [0] = 0 in both; v = max(b, g, r), vmin = min(b, g, r), diff = v - vmin;
+ *     s = (diff * sdiv[v] + 2048) >> 12; h = (v == r) ? g - b : (v == g) ? b - r + 2 * diff : r - g + 4 * diff; h = (h * hdiv[diff] + 2048) >> 12;
+ *     if h < 0, h += 180; all three saturated to 0 .. 255.
+ *     HSV2RGB, restated (fp32, every operation rounded separately, + - x and floorf only): hf = (float)h, sf = s * (1.f / 255.f),
+ *     vf = v * (1.f / 255.f).  s == 0: r = g = b = vf.  Otherwise hf *= (6.f / 180.f); while hf >= 6, hf -= 6; sector = (int)floorf(hf), hf -= sector;
+ *     a sector outside 0 .. 5 -> sector = 0, hf = 0; tab = {vf, vf * (1 - sf), vf * (1 - sf * hf), vf * (1 - sf * (1 - hf))};
+ *     (b, g, r) = tab[{1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0}][sector].  Each output is clamp(cvRound(x * 255.f), 0, 255).
+ * (d) out[b][c][y][x] = lut[b][c][level of plane c].
+ * The recipes of (b) and (c) are restated from memory: agreement with a real cv2.blur / cv2.cvtColor is UNVERIFIED (OpenCV is not available where
+ * this was written); what is tested is that device, host and an independent numpy restatement agree bit for bit, that the conversions are within
+ * one level of the textbook HSV formulas in fp64, and that the blur is the fp64 box mean over reflect-101 padding.
+ * Integer arithmetic, one fp64 product and exactly rounded fp32 operations: bit-identical on device and host.
+ * B == 0: nothing is launched.  B > 65535: Y2_ENOSUP.  W > Y2_COLLATE_MAX_W: Y2_EINVAL.  16-byte stores when W % 4 == 0 and out is 16-byte aligned,
+ * 4-byte stores otherwise.  Never allocates, never synchronises.  The tables are DEVICE memory: the device entry point cannot refuse a window
+ * outside its image, a blur size outside 1 .. Y2_JITTER_MAX_BLUR or hsv without hsv_tab (utils.data.to_device and the host function do: Y2_EINVAL);
+ * it keeps every tap inside the image the table names, brings a blur size into that range and takes the plain path when hsv_tab is NULL. */
+#define Y2_JITTER_MAX_BLUR 7
+int y2_collate_jitter_images(const uint8_t* src, const int64_t* offset, const int32_t* geom, const int32_t* jitter, const uint8_t* hsv_tab,
+                             const float* lut, int32_t B, int32_t H, int32_t W, int32_t flags, float* out, y2_stream_t stream);
+
 /* batch_iou_matrix: [Bt,N1,2]x2, [Bt,N2,2]x2 -> out [Bt,N1,N2]; iou_matrix is Bt = 1.  min_union = eps32.
  * mode 0: IoU (utils/iou/torch.py:47-61, 139-153);  mode 1: intersection area only (:24-44, 116-136). */
 int y2_iou_matrix(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
@@ -392,6 +428,11 @@ int y2_collate_images_host(const uint8_t* src, const int64_t* offset, const int3
 int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src_offset, const int32_t* src_geom, const double* inv,
                                uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
                                int32_t B, int32_t max_h, int32_t max_w, int32_t fill);
+/* y2_collate_jitter_images on host memory (utils.data.to_device on 'cpu'): the same arithmetic, bit-identical output.  The tables are checked first
+ * (those of y2_collate_images_host; kx and ky in 1 .. Y2_JITTER_MAX_BLUR, hsv 0 or 1, jitter[b][3] == 0, hsv_tab present when an image sets hsv):
+ * Y2_EINVAL, nothing is written. */
+int y2_collate_jitter_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const int32_t* jitter, const uint8_t* hsv_tab,
+                                  const float* lut, int32_t B, int32_t H, int32_t W, int32_t flags, float* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic mode (opt-in, process-global; one process per GPU, one stream).  By default the split-K weight gradient, the

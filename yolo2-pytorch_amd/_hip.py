@@ -59,6 +59,7 @@ MULTI_ZERO, MULTI_F64_TO_F32, MULTI_COPY = 0, 1, 2
 EVAL_MATCH_MAX_G = 1024      # Y2_EVAL_MATCH_MAX_G (include/yolo2_hip.h)
 COLLATE_MAX_W = 4096         # Y2_COLLATE_MAX_W
 WARP_MAX_DIM = 16384         # Y2_WARP_MAX_DIM
+JITTER_MAX_BLUR = 7          # Y2_JITTER_MAX_BLUR
 
 SIGNATURES = {
     'y2_abi_version': [],
@@ -137,6 +138,8 @@ SIGNATURES = {
     'y2_collate_images_host': [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_warp_affine_images': [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_warp_affine_images_host': [c_void_p] * 7 + [c_int, c_int, c_int, c_int],
+    'y2_collate_jitter_images': [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    'y2_collate_jitter_images_host': [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_set_deterministic': [c_int, c_void_p, ctypes.c_longlong],
     'y2_get_deterministic': [],
     'y2_colstats_det': [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
@@ -431,7 +434,7 @@ def kernel_hash():
     """sha256 (16 hex digits) of the kernel sources the library is built from; None when the sources are not there."""
     import glob
     import hashlib
-    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
+    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
     if len(files) < 3 or not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha256()

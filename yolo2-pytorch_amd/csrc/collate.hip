@@ -9,31 +9,13 @@
 // A streaming kernel: per output value 4 gathered source bytes (served by the caches: neighbouring outputs share taps) and one 4-byte store; the
 // fp32 output is 4/3 .. 4x the bytes of the source, so the 16-byte stores are what has to be right.
 #include "common.h"
+#include "resample.h"
 
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CL_ROWS = 16;         // output rows per workgroup: 416x416 x 64 images -> 1664 workgroups, 6-7 items of 4 pixels per thread
-
-// Tap k (first of two; the second is k + 1, both clamped by the caller) and 11-bit coefficients of destination index i on an axis that maps a window
-// of s source pixels to d destination pixels.  `edge`: the horizontal axis pins k to the window and zeroes the fraction there; the vertical axis only
-// clamps its taps (the two coefficients always sum to 2048, so equal taps give the pixel back).
-__device__ inline void cl_axis(int i, int s, int d, bool edge, int& k, int& c0, int& c1) {
-    const double scale = (double)s / (double)d;
-    float f = (float)(((double)i + 0.5) * scale - 0.5);
-    const float fl = floorf(f);
-    k = (int)fl;
-    f -= fl;
-    if (edge) {
-        if (k < 0) { k = 0; f = 0.f; }
-        if (k >= s - 1) { k = s - 1; f = 0.f; }
-    }
-    c1 = (int)rintf(f * 2048.f);
-    c0 = (int)rintf((1.f - f) * 2048.f);
-}
-
-__device__ inline int cl_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct CollateArgs {
     const uint8_t* src; const int64_t* offset; const int32_t* geom; const float* lut;
@@ -63,23 +45,10 @@ __global__ __launch_bounds__(256) void collate_images_kernel(const CollateArgs a
     const int row_first = blockIdx.x * CL_ROWS;
     const int rows = min(CL_ROWS, H - row_first);
     for (int x = t; x < W; x += 256) {
-        int k, c0, c1;
-        if (box) { k = 2 * x; c0 = c1 = 0; }
-        else cl_axis(x, ww, W, true, k, c0, c1);
-        int s0 = wx0 + cl_clamp(k, 0, ww - 1), s1 = wx0 + cl_clamp(k + 1, 0, ww - 1);
-        if (flip) { s0 = src_w - 1 - s0; s1 = src_w - 1 - s1; }
-        // a window inside the image never moves here: whatever the table says, no tap leaves the image it names
-        x_off0[x] = 3 * cl_clamp(s0, 0, src_w - 1);
-        x_off1[x] = 3 * cl_clamp(s1, 0, src_w - 1);
-        x_coef[x] = c0 | (c1 << 16);
+        cl_col(x, box, ww, W, wx0, flip, src_w, x_off0[x], x_off1[x], x_coef[x]);
     }
     for (int r = t; r < rows; r += 256) {
-        int k, c0, c1;
-        if (box) { k = 2 * (row_first + r); c0 = c1 = 0; }
-        else cl_axis(row_first + r, wh, H, false, k, c0, c1);
-        y_row0[r] = cl_clamp(wy0 + cl_clamp(k, 0, wh - 1), 0, src_h - 1);
-        y_row1[r] = cl_clamp(wy0 + cl_clamp(k + 1, 0, wh - 1), 0, src_h - 1);
-        y_coef[r] = c0 | (c1 << 16);
+        cl_row(row_first + r, box, wh, H, wy0, src_h, y_row0[r], y_row1[r], y_coef[r]);
     }
     for (int i = t; i < 768; i += 256) lut[i] = a.lut[i];
     __syncthreads();
@@ -87,14 +56,6 @@ __global__ __launch_bounds__(256) void collate_images_kernel(const CollateArgs a
     const size_t plane = (size_t)H * W;
     float* out = a.out + (size_t)b * 3 * plane;
     const int cs = a.swap ? 2 : 0;          // output plane c reads source channel c ^ cs for c in {0, 2}; channel 1 stays
-    // level of one output value: taps at byte offsets o0 / o1 (channel included) of source rows p0 / p1
-    auto level = [&](const uint8_t* p0, const uint8_t* p1, int o0, int o1, int c, int b0, int b1) -> int {
-        if (box) return ((int)p0[o0] + (int)p0[o1] + (int)p1[o0] + (int)p1[o1] + 2) >> 2;
-        const int c0 = c & 0xffff, c1 = c >> 16;
-        const int h0 = (int)p0[o0] * c0 + (int)p0[o1] * c1;
-        const int h1 = (int)p1[o0] * c0 + (int)p1[o1] * c1;
-        return cl_clamp((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2, 0, 255);
-    };
     if (a.vec) {
         // W % 4 == 0: the three column tables start on 16-byte boundaries and a lane's 4 columns are ONE 16-byte LDS read per table (a wave reads
         // 1 KB of consecutive addresses: no bank conflict; four 4-byte reads per lane at a stride of 16 bytes would be 4-way conflicts)
@@ -112,7 +73,7 @@ __global__ __launch_bounds__(256) void collate_images_kernel(const CollateArgs a
                 const int ch = c == 1 ? 1 : c ^ cs;
                 f32x4 v;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = lut[c * 256 + level(p0, p1, o0[j] + ch, o1[j] + ch, xc[j], b0, b1)];
+                for (int j = 0; j < 4; ++j) v[j] = lut[c * 256 + cl_level(box, p0, p1, o0[j] + ch, o1[j] + ch, xc[j], b0, b1)];
                 *reinterpret_cast<f32x4*>(o + c * plane) = v;
             }
         }
@@ -127,7 +88,7 @@ __global__ __launch_bounds__(256) void collate_images_kernel(const CollateArgs a
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const int ch = c == 1 ? 1 : c ^ cs;
-                o[c * plane] = lut[c * 256 + level(p0, p1, o0 + ch, o1 + ch, xc, b0, b1)];
+                o[c * plane] = lut[c * 256 + cl_level(box, p0, p1, o0 + ch, o1 + ch, xc, b0, b1)];
             }
         }
     }

@@ -1,5 +1,5 @@
 // host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
-// y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host).
+// y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host, y2_collate_jitter_images_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "yolo2_hip.h"
+#include "resample.h"
 
 namespace {
 
@@ -29,23 +30,6 @@ inline float iou_host(float ymin1, float xmin1, float ymax1, float xmax1, float 
 }
 
 inline float nms_key(float s) { return s != s ? -INFINITY : s; }   // NaN ranks last (detect.hip: nms_key)
-
-// collate.hip: cl_axis, operation for operation (exactly rounded IEEE operations only: the device gives the same bits)
-inline void collate_axis(int i, int s, int d, bool edge, int& k, int& c0, int& c1) {
-    const double scale = (double)s / (double)d;
-    float f = (float)(((double)i + 0.5) * scale - 0.5);
-    const float fl = floorf(f);
-    k = (int)fl;
-    f -= fl;
-    if (edge) {
-        if (k < 0) { k = 0; f = 0.f; }
-        if (k >= s - 1) { k = s - 1; f = 0.f; }
-    }
-    c1 = (int)rintf(f * 2048.f);
-    c0 = (int)rintf((1.f - f) * 2048.f);
-}
-
-inline int collate_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // warp.hip: wp_round, wp_clamp16 (rint rounds to nearest even in the default rounding mode, which nothing here changes)
 inline long long warp_round(double v) { return (long long)(int)fmin(fmax(rint(v), -2147483648.0), 2147483647.0); }
@@ -195,41 +179,24 @@ extern "C" int y2_collate_images_host(const uint8_t* src, const int64_t* offset,
     }
     const int cs = (flags & 1) ? 2 : 0;
     const size_t plane = (size_t)H * W;
-    std::vector<int> off0((size_t)W), off1((size_t)W), xc0((size_t)W), xc1((size_t)W);
+    std::vector<int> off0((size_t)W), off1((size_t)W), xc((size_t)W);
     for (int b = 0; b < B; ++b) {
         const int32_t* g = geom + 8 * (size_t)b;
-        const int stride = g[0], src_w = g[2], wy0 = g[3], wx0 = g[4], wh = g[5], ww = g[6], flip = g[7];
+        const int stride = g[0], src_h = g[1], src_w = g[2], wy0 = g[3], wx0 = g[4], wh = g[5], ww = g[6], flip = g[7];
         const bool box = wh == 2 * H && ww == 2 * W;
-        for (int x = 0; x < W; ++x) {
-            int k, c0, c1;
-            if (box) { k = 2 * x; c0 = c1 = 0; }
-            else collate_axis(x, ww, W, true, k, c0, c1);
-            int s0 = wx0 + collate_clamp(k, 0, ww - 1), s1 = wx0 + collate_clamp(k + 1, 0, ww - 1);
-            if (flip) { s0 = src_w - 1 - s0; s1 = src_w - 1 - s1; }
-            off0[(size_t)x] = 3 * s0; off1[(size_t)x] = 3 * s1; xc0[(size_t)x] = c0; xc1[(size_t)x] = c1;
-        }
+        for (int x = 0; x < W; ++x) cl_col(x, box, ww, W, wx0, flip, src_w, off0[(size_t)x], off1[(size_t)x], xc[(size_t)x]);
         const uint8_t* img = src + offset[b];
         float* o = out + (size_t)b * 3 * plane;
         for (int y = 0; y < H; ++y) {
-            int k, b0, b1;
-            if (box) { k = 2 * y; b0 = b1 = 0; }
-            else collate_axis(y, wh, H, false, k, b0, b1);
-            const uint8_t* p0 = img + (long long)(wy0 + collate_clamp(k, 0, wh - 1)) * stride;
-            const uint8_t* p1 = img + (long long)(wy0 + collate_clamp(k + 1, 0, wh - 1)) * stride;
+            int r0, r1, yc;
+            cl_row(y, box, wh, H, wy0, src_h, r0, r1, yc);
+            const uint8_t* p0 = img + (long long)r0 * stride;
+            const uint8_t* p1 = img + (long long)r1 * stride;
             for (int c = 0; c < 3; ++c) {
                 const int ch = c == 1 ? 1 : c ^ cs;
                 float* row = o + c * plane + (size_t)y * W;
-                for (int x = 0; x < W; ++x) {
-                    const int o0 = off0[(size_t)x] + ch, o1 = off1[(size_t)x] + ch;
-                    int level;
-                    if (box) level = ((int)p0[o0] + (int)p0[o1] + (int)p1[o0] + (int)p1[o1] + 2) >> 2;
-                    else {
-                        const int h0 = (int)p0[o0] * xc0[(size_t)x] + (int)p0[o1] * xc1[(size_t)x];
-                        const int h1 = (int)p1[o0] * xc0[(size_t)x] + (int)p1[o1] * xc1[(size_t)x];
-                        level = collate_clamp((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2, 0, 255);
-                    }
-                    row[x] = lut[c * 256 + level];
-                }
+                for (int x = 0; x < W; ++x)
+                    row[x] = lut[c * 256 + cl_level(box, p0, p1, off0[(size_t)x] + ch, off1[(size_t)x] + ch, xc[(size_t)x], yc & 0xffff, yc >> 16)];
             }
         }
     }
@@ -280,6 +247,84 @@ extern "C" int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src
                 }
             }
         }
+    }
+    return Y2_OK;
+}
+
+// y2_collate_jitter_images on host memory (jitter.hip: collate_jitter_images_kernel, image by image instead of tile by tile).  The tables are readable
+// here, so they are checked before anything is written.
+extern "C" int y2_collate_jitter_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const int32_t* jitter, const uint8_t* hsv_tab,
+                                             const float* lut, int32_t B, int32_t H, int32_t W, int32_t flags, float* out) {
+    if (B < 0 || H <= 0 || W <= 0 || W > Y2_COLLATE_MAX_W || (flags & ~1)) return Y2_EINVAL;
+    if (B == 0) return Y2_OK;
+    if (B > 65535) return Y2_ENOSUP;
+    if (!src || !offset || !geom || !jitter || !lut || !out) return Y2_EINVAL;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* g = geom + 8 * (size_t)b;
+        const int32_t* jt = jitter + 4 * (size_t)b;
+        const long long stride = g[0], src_h = g[1], src_w = g[2], wy0 = g[3], wx0 = g[4], wh = g[5], ww = g[6];
+        if (offset[b] < 0 || src_h < 1 || src_w < 1 || stride < 3 * src_w || wh < 1 || ww < 1 || wy0 < 0 || wx0 < 0 || wy0 + wh > src_h || wx0 + ww > src_w
+            || (g[7] != 0 && g[7] != 1))
+            return Y2_EINVAL;
+        if (jt[0] < 1 || jt[0] > Y2_JITTER_MAX_BLUR || jt[1] < 1 || jt[1] > Y2_JITTER_MAX_BLUR || (jt[2] != 0 && jt[2] != 1) || jt[3] != 0 || (jt[2] && !hsv_tab))
+            return Y2_EINVAL;
+    }
+    int sdiv[256], hdiv[256];
+    for (int i = 0; i < 256; ++i) { sdiv[i] = jt_div(JT_SDIV_N, i); hdiv[i] = jt_div(JT_HDIV_N, i); }
+    const size_t plane = (size_t)H * W;
+    std::vector<int> off0((size_t)W), off1((size_t)W), xc((size_t)W), rx((size_t)W + Y2_JITTER_MAX_BLUR);
+    std::vector<uint8_t> lv(plane * 3);          // the resized image [H][W][3], source channel order
+    std::vector<int> rs(plane * 3);              // its row sums
+    for (int b = 0; b < B; ++b) {
+        const int32_t* g = geom + 8 * (size_t)b;
+        const int32_t* jt = jitter + 4 * (size_t)b;
+        const int stride = g[0], src_h = g[1], src_w = g[2], wy0 = g[3], wx0 = g[4], wh = g[5], ww = g[6], flip = g[7];
+        const int kx = jt[0], ky = jt[1], hsv = jt[2];
+        const bool box = wh == 2 * H && ww == 2 * W;
+        for (int x = 0; x < W; ++x) cl_col(x, box, ww, W, wx0, flip, src_w, off0[(size_t)x], off1[(size_t)x], xc[(size_t)x]);
+        const uint8_t* img = src + offset[b];
+        for (int y = 0; y < H; ++y) {
+            int r0, r1, yc;
+            cl_row(y, box, wh, H, wy0, src_h, r0, r1, yc);
+            const uint8_t* p0 = img + (long long)r0 * stride;
+            const uint8_t* p1 = img + (long long)r1 * stride;
+            for (int x = 0; x < W; ++x)
+                for (int c = 0; c < 3; ++c)
+                    lv[((size_t)y * W + x) * 3 + c] = (uint8_t)cl_level(box, p0, p1, off0[(size_t)x] + c, off1[(size_t)x] + c, xc[(size_t)x], yc & 0xffff, yc >> 16);
+        }
+        // the box filter: the window of column x is x - kx / 2 .. x - kx / 2 + kx - 1, reflected into the resized image; rows alike
+        for (int i = 0; i < W + kx - 1; ++i) rx[(size_t)i] = jt_reflect101(i - kx / 2, W);
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x)
+                for (int c = 0; c < 3; ++c) {
+                    int s = 0;
+                    for (int i = 0; i < kx; ++i) s += lv[((size_t)y * W + rx[(size_t)(x + i)]) * 3 + c];
+                    rs[((size_t)y * W + x) * 3 + c] = s;
+                }
+        const double inv = 1.0 / (double)(kx * ky);
+        const float* tab = lut + (size_t)b * 768;
+        const uint8_t* ht = hsv ? hsv_tab + (size_t)b * 768 : nullptr;
+        float* o = out + (size_t)b * 3 * plane;
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x) {
+                int lev[3];
+                for (int c = 0; c < 3; ++c) {
+                    int s = 0;
+                    for (int j = 0; j < ky; ++j) s += rs[((size_t)jt_reflect101(y + j - ky / 2, H) * W + x) * 3 + c];
+                    lev[c] = kx * ky > 1 ? jt_blur_level(s, inv) : s;
+                }
+                int p[3];          // the levels of the three output planes
+                if (hsv) {
+                    int h, s, v;
+                    jt_bgr2hsv(lev[0], lev[1], lev[2], sdiv, hdiv, h, s, v);
+                    jt_hsv2rgb(ht[h], ht[256 + s], ht[512 + v], p[0], p[1], p[2]);
+                } else {
+                    p[0] = (flags & 1) ? lev[2] : lev[0];
+                    p[1] = lev[1];
+                    p[2] = (flags & 1) ? lev[0] : lev[2];
+                }
+                for (int c = 0; c < 3; ++c) o[c * plane + (size_t)y * W + x] = tab[c * 256 + p[c]];
+            }
     }
     return Y2_OK;
 }

@@ -12,6 +12,10 @@ y2_warp_affine_images (`src_offset`, `src_geom`, `warp`: the inverse matrices, `
 images inside an intermediate device buffer, and `to_device` launches the warp in front of the collate kernel.  A batch without a rotated sample
 is untouched by all this: the same keys, the same bytes, one launch.
 
+With `transform_image` (transform.image.get_transform: RandomBlur, the HSV chain, RandomGamma) `Collate` draws every sample's jitter after its resize
+transform and adds `jitter`, `hsv_tab` (when the sequence goes through HSV) and `lut_b`, and `to_device` launches y2_collate_jitter_images IN PLACE
+of y2_collate_images (behind the warp launch, when there is one).  Without it, or with a sequence that is only BGR2RGB, nothing changes.
+
 What ships to the device is the source pixels as cv2.imread returned them - a quarter to a third of the bytes of the finished fp32 tensor."""
 import os
 import pickle
@@ -81,6 +85,19 @@ def check_warp(src_offset, src_geom, warp, src_bytes, offset, geom, rot_bytes):
                          'offset %d of %d bytes, geom %s, warp %s)' % (b, src_offset[b], src_bytes, src_geom[b].tolist(), offset[b], rot_bytes, geom[b, :3].tolist(), warp[b].tolist()))
 
 
+def check_jitter(jitter, hsv_tab, lut_b, B):
+    """The tables of y2_collate_jitter_images (host arrays; hsv_tab may be None): shapes, blur sizes in 1 .. Y2_JITTER_MAX_BLUR, hsv 0 or 1."""
+    jitter = np.asarray(jitter)
+    if jitter.shape != (B, 4) or jitter.dtype != np.int32 or tuple(lut_b.shape) != (B, 3, 256) or (hsv_tab is not None and tuple(hsv_tab.shape) != (B, 3, 256)):
+        raise ValueError('jitter: jitter must be int32 [B, 4], hsv_tab uint8 [B, 3, 256] and lut_b fp32 [B, 3, 256]')
+    kx, ky, hsv, zero = jitter.T.astype(np.int64)
+    limit = _hip.JITTER_MAX_BLUR
+    bad = (kx < 1) | (kx > limit) | (ky < 1) | (ky > limit) | ((hsv != 0) & (hsv != 1)) | (zero != 0) | ((hsv != 0) & (hsv_tab is None))
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError('jitter: image %d: blur size outside 1 .. %d, hsv not 0 / 1 or hsv without hsv_tab (jitter %s)' % (b, limit, jitter[b].tolist()))
+
+
 ROT_ROW_ALIGN, ROT_IMAGE_ALIGN = 16, 64      # the layout of the rotated images is Collate's: rows and images start where the warp kernel's 12-byte stores are aligned
 
 
@@ -90,13 +107,16 @@ class Collate(object):
     sizes: the (height, width) pairs a batch's size is drawn from with random.choice; a drawn size serves `maintain` further batches.
     swap_rb: the images are BGR (cv2.imread) and the network reads RGB (transform.image.BGR2RGB).
     normalize: (mean, std) of transform.image.Normalize after ToTensor; None: ToTensor only.
+    transform_image: the object of transform.image.get_transform; called once per sample after its resize transform (the reference's order of
+    draws).  `swap_rb` then comes from its sequence.  None: no jitter.
     dir: where the sample that raised is pickled before the exception goes on."""
 
-    def __init__(self, resize, sizes, maintain=1, swap_rb=True, normalize=(0.5, 1.0), dir=None):
+    def __init__(self, resize, sizes, maintain=1, swap_rb=True, normalize=(0.5, 1.0), dir=None, transform_image=None):
         if maintain <= 0:
             raise ValueError('Collate: maintain must be positive')
         self.resize, self.sizes, self.maintain, self.dir = resize, sizes, maintain, dir
-        self.swap_rb = bool(swap_rb)
+        self.transform_image = transform_image
+        self.swap_rb = bool(swap_rb) if transform_image is None else bool(transform_image.swap_rb)
         self.normalize = None if normalize is None else (float(normalize[0]), float(normalize[1]))
         self._repeats_left = 0
 
@@ -113,6 +133,8 @@ class Collate(object):
         image = data['image']
         if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
             raise ValueError('collate: an image must be uint8 [h, w, 3] (got %s %s)' % (image.dtype, image.shape))
+        if self.transform_image is not None and self.transform_image.active:
+            data['jitter'] = self.transform_image()
         return data
 
     def _keep(self, data):
@@ -162,6 +184,15 @@ class Collate(object):
             check_warp(src_offset, src_geom, warp, raw.size, offset, geom, pos)
             extra = dict(src_offset=torch.from_numpy(src_offset), src_geom=torch.from_numpy(src_geom), warp=torch.from_numpy(warp), rot_bytes=pos,
                        rot_size=(int(geom[:, 1].max()), int(geom[:, 2].max())))
+        if self.transform_image is not None and self.transform_image.active:
+            records = [data['jitter'] for data in samples]
+            jitter = np.array([tuple(r['blur']) + (int(r['hsv']), 0) for r in records], np.int32).reshape(-1, 4)
+            level = level_table(self.normalize, 'cpu')
+            extra['jitter'] = torch.from_numpy(jitter)
+            if self.transform_image.hsv:
+                extra['hsv_tab'] = torch.from_numpy(np.stack([np.stack([r['h'], r['s'], r['v']]) for r in records]).astype(np.uint8))
+            extra['lut_b'] = torch.stack([level[:, torch.from_numpy(r['gamma'].astype(np.int64))] for r in records])      # lut_b[b, c, l] = level[c, gamma_b[l]]
+            check_jitter(jitter, extra.get('hsv_tab'), extra['lut_b'], len(samples))
         check_geometry(offset, geom, pos)
         out.update(raw=torch.from_numpy(raw), offset=torch.from_numpy(offset), geom=torch.from_numpy(geom), size=(height, width),
                    swap_rb=self.swap_rb, normalize=self.normalize)
@@ -200,7 +231,9 @@ def to_device(batch, device=None, out=None, rot=None):
     A batch with `warp` (a sample was rotated) takes TWO launches: y2_warp_affine_images writes every rotated uint8 image into an intermediate buffer
     of `batch['rot_bytes']` bytes - `rot`, a contiguous uint8 tensor of at least that size on `device` (a captured graph's static buffer), or a fresh
     torch.empty - and y2_collate_images reads that buffer instead of `raw`.  The result carries it as `rot`.  `batch['fill']` (0xC2C1C0, one byte per
-    source channel; default 0, what the reference passes) is the level outside the source.  Without `warp`, `rot` is not touched."""
+    source channel; default 0, what the reference passes) is the level outside the source.  Without `warp`, `rot` is not touched.
+    A batch with `jitter` (Collate had a transform_image) launches y2_collate_jitter_images instead of y2_collate_images: `jitter` int32 [B, 4],
+    `hsv_tab` uint8 [B, 3, 256] (optional) and `lut_b` fp32 [B, 3, 256], the per-image table that takes the place of `lut`."""
     raw = batch['raw']
     if device is None:
         device = raw.device if raw.is_cuda else torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
@@ -214,6 +247,9 @@ def to_device(batch, device=None, out=None, rot=None):
         check_geometry(batch['offset'].numpy(), batch['geom'].numpy(), pixels)
         if warped and not any(batch[k].is_cuda for k in ('src_offset', 'src_geom', 'warp')):
             check_warp(batch['src_offset'].numpy(), batch['src_geom'].numpy(), batch['warp'].numpy(), raw.numel(), batch['offset'].numpy(), batch['geom'].numpy(), pixels)
+    jittered = 'jitter' in batch
+    if jittered and not any(batch[k].is_cuda for k in ('jitter', 'hsv_tab', 'lut_b') if k in batch):
+        check_jitter(batch['jitter'].numpy(), batch.get('hsv_tab'), batch['lut_b'], batch['geom'].size(0))
     res = {k: (v.to(device, non_blocking=v.is_pinned()) if torch.is_tensor(v) else v) for k, v in batch.items()}
     raw, offset, geom = res['raw'], res['offset'], res['geom']
     B = geom.size(0)
@@ -223,7 +259,13 @@ def to_device(batch, device=None, out=None, rot=None):
         raise ValueError('to_device: size %dx%d (the width is limited to %d)' % (H, W, _hip.COLLATE_MAX_W))
     raw, offset, geom = raw.contiguous(), offset.contiguous(), geom.contiguous()
     lut = res.get('lut')
-    if lut is None:
+    if jittered:
+        jitter, hsv_tab, lut = res['jitter'].contiguous(), res.get('hsv_tab'), res['lut_b'].contiguous()
+        hsv_tab = None if hsv_tab is None else hsv_tab.contiguous()
+        if (jitter.dtype != torch.int32 or tuple(jitter.shape) != (B, 4) or lut.dtype != torch.float32 or tuple(lut.shape) != (B, 3, 256)
+                or (hsv_tab is not None and (hsv_tab.dtype != torch.uint8 or tuple(hsv_tab.shape) != (B, 3, 256)))):
+            raise ValueError('to_device: jitter must be int32 [B, 4], hsv_tab uint8 [B, 3, 256], lut_b fp32 [B, 3, 256]')
+    elif lut is None:
         lut = level_table(batch.get('normalize', (0.5, 1.0)), device)
     elif lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
         raise ValueError('to_device: lut must be a contiguous fp32 [3, 256] tensor')
@@ -247,15 +289,17 @@ def to_device(batch, device=None, out=None, rot=None):
         warp_args = (raw.data_ptr(), src_offset.data_ptr(), src_geom.data_ptr(), inv.data_ptr(), rot.data_ptr(), offset.data_ptr(), geom.data_ptr(),
                      B, max_h, max_w, int(batch.get('fill', 0)))
         raw = res['rot'] = rot
-    args = (raw.data_ptr(), offset.data_ptr(), geom.data_ptr(), lut.data_ptr(), B, H, W, 1 if batch.get('swap_rb', True) else 0, out.data_ptr())
+    tables = (jitter.data_ptr(), None if hsv_tab is None else hsv_tab.data_ptr(), lut.data_ptr()) if jittered else (lut.data_ptr(),)
+    args = (raw.data_ptr(), offset.data_ptr(), geom.data_ptr()) + tables + (B, H, W, 1 if batch.get('swap_rb', True) else 0, out.data_ptr())
+    name = 'y2_collate_jitter_images' if jittered else 'y2_collate_images'
     if device.type == 'cuda':
         with torch.cuda.device(device):
             if warped:
                 _hip.check(_hip.lib().y2_warp_affine_images(*warp_args, _hip.stream()), 'y2_warp_affine_images')
-            _hip.check(_hip.lib().y2_collate_images(*args, _hip.stream()), 'y2_collate_images')
+            _hip.check(getattr(_hip.lib(), name)(*args, _hip.stream()), name)
     else:
         if warped:
             _hip.check(_hip.lib().y2_warp_affine_images_host(*warp_args), 'y2_warp_affine_images_host')
-        _hip.check(_hip.lib().y2_collate_images_host(*args), 'y2_collate_images_host')
+        _hip.check(getattr(_hip.lib(), name + '_host')(*args), name + '_host')
     res['tensor'] = out
     return res
