@@ -335,3 +335,51 @@ def test_conv_wgrad_runs_the_choice_it_is_given(tune_defaults, monkeypatch):
     assert run(choice=2, dz_pre=True, native=native) == (native, ['y2_wino_wgrad_ex'])
     with pytest.raises(AssertionError):
         run(choice=0, dz_pre=True)                                                      # a transformed gradient serves the 4x4-tile form only
+
+
+def _fields(p):
+    return {name: getattr(p, name) for name, _ in type(p)._fields_}
+
+
+def test_conv_params_filler_writes_each_family_form_and_nothing_else():
+    """model._infer_parts.conv_params on CPU tensors (addresses only; nothing is launched): Darknet's pooled form leaves stride / pad_plus1 unset -
+    they are part of _hip.autotune_conv's key and so of every entry of the committed table -, a ResNet stride-2 residual form and DenseNet's
+    channel-offset form set them; every other field is what was asked for or zero."""
+    import json
+    import torch
+    import _hip
+    from model._infer_parts import conv_params
+    x, w, scale, shift, y, yp, r = [torch.zeros(8) for _ in range(7)]
+    zero = dict.fromkeys([name for name, _ in _hip.ConvParams._fields_], 0)
+    zero.update(dict.fromkeys(['x', 'w', 'scale', 'shift', 'y', 'y_pool', 'stats', 'workspace', 'residual'], None))
+
+    # Darknet, last layer of layers1: full-resolution output for the passthrough and the pooled one for layers2
+    p, f = conv_params(x, w, scale, shift, 2, 8, 12, 16, 16, 32, 3, 0.1, y=y, y_pool=yp, ldy=32, ldp=32)
+    assert p.stride == 0 and p.pad_plus1 == 0
+    assert _fields(p) == dict(zero, x=x.data_ptr(), w=w.data_ptr(), scale=scale.data_ptr(), shift=shift.data_ptr(), y=y.data_ptr(), y_pool=yp.data_ptr(),
+                              B=2, H=8, W=12, Cin=16, ldx=16, Cout=32, ksize=3, ldy=32, ldp=32, slope=_hip.c_float(0.1).value)
+    assert f == 2.0 * 16 * 32 * 9 * 2 * 8 * 12
+    # the passthrough's reorg'ed output at a channel offset of the concat buffer, no BatchNorm: bias only
+    p, _ = conv_params(x, w, None, shift, 2, 8, 12, 16, 16, 4, 1, 1.0, y=y, ldy=48, coff=16, poff=3, out_mode=1)
+    assert _fields(p) == dict(zero, x=x.data_ptr(), w=w.data_ptr(), shift=shift.data_ptr(), y=y.data_ptr(),
+                              B=2, H=8, W=12, Cin=16, ldx=16, Cout=4, ksize=1, ldy=48, coff=16, poff=3, out_mode=1, slope=1.0)
+
+    # ResNet: the 3x3 stride-2 convolution that ends a block, residual added in the epilogue; the stem's 3 input channels are packed as 4
+    pad = 1
+    p, f = conv_params(x, w, scale, shift, 2, 9, 13, 4, 4, 8, 3, 0.0, y=y, ldy=8, residual=r, ldr=8, stride=2, pad=pad, real_cin=3)
+    assert p.stride == 2 and p.pad_plus1 == pad + 1 and p.residual == r.data_ptr() and p.ldr == 8
+    assert _fields(p) == dict(zero, x=x.data_ptr(), w=w.data_ptr(), scale=scale.data_ptr(), shift=shift.data_ptr(), y=y.data_ptr(), residual=r.data_ptr(),
+                              B=2, H=9, W=13, Cin=4, ldx=4, Cout=8, ksize=3, ldy=8, ldr=8, stride=2, pad_plus1=2)
+    assert f == 2.0 * 3 * 8 * 9 * 2 * 5 * 7          # over the real input channels and the 5x7 output
+    # without a residual ldr stays unset
+    assert conv_params(x, w, scale, shift, 2, 9, 13, 4, 4, 8, 3, 0.0, y=y, ldy=8, ldr=8, stride=2, pad=pad)[0].ldr == 0
+
+    # DenseNet: a layer's raw 3x3 writes its growth_rate channels at its offset of the block buffer
+    p, f = conv_params(x, w, None, None, 2, 8, 8, 12, 12, 6, 3, 1.0, y=y, ldy=40, coff=22, stride=1, pad=1)
+    assert p.coff == 22 and p.ldy == 40
+    assert _fields(p) == dict(zero, x=x.data_ptr(), w=w.data_ptr(), y=y.data_ptr(),
+                              B=2, H=8, W=8, Cin=12, ldx=12, Cout=6, ksize=3, ldy=40, coff=22, slope=1.0, stride=1, pad_plus1=2)
+    assert f == 2.0 * 12 * 6 * 9 * 2 * 8 * 8
+
+    # the committed table was measured on these kernel sources: a Python-side change must not make it stale
+    assert _hip.kernel_hash() == json.load(open(_hip.DEFAULTS_PATH))['kernels']

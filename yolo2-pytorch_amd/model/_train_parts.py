@@ -6,9 +6,8 @@ import ctypes
 import torch
 
 import _hip
+from model._infer_parts import BN_EPS, LEAKY, fold_bn  # noqa: F401 (LEAKY: re-exported to the two graphs)
 
-BN_EPS = 1e-5
-LEAKY = 0.1
 BN_MOMENTUM = 0.01          # Darknet and Tiny (model/yolo2.py)
 PLUGIN_MOMENTUM = 0.1       # the ResNet, MobileNet and DenseNet plugins (nn.BatchNorm2d's default)
 
@@ -107,10 +106,10 @@ def bn_params(L, st, dev, bn, stats, count, C, frozen, momentum, tensors=None):
     and copying stand-ins back - is the caller's."""
     gamma, beta, rm, rv = tensors if tensors is not None else (bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var)
     gamma, beta = _hip.f32c(gamma), _hip.f32c(beta)
-    scale, shift = _new(dev, C), _new(dev, C)
     if frozen:
-        _hip.check(L.y2_bn_fold(_hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(_hip.f32c(rm)), _hip.ptr(_hip.f32c(rv)), BN_EPS, _hip.ptr(scale), _hip.ptr(shift), C, st), 'y2_bn_fold')
+        scale, shift = fold_bn(L, st, dev, bn, (gamma, beta, rm, rv), C)
         return scale, shift, _hip.f32c(rm), torch.rsqrt(_hip.f32c(rv) + BN_EPS)
+    scale, shift = _new(dev, C), _new(dev, C)
     mean, invstd = _new(dev, C), _new(dev, C)
     counter = _counter(bn)
     covered = 0

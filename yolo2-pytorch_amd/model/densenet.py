@@ -15,7 +15,9 @@ pre-affine + ReLU in the operand loader, norm2 + ReLU in the epilogue), then the
 one y2_preact_conv1x1_fwd launch with pool = 1 (the 2x2 average is taken on the pre-activated input: a 1x1 convolution and an average pool
 commute) into the next block buffer.  The head is y2_preact_conv1x1_fwd with norm5 as the pre-affine (no ReLU, model/densenet.py:53-54) and the
 bias in the epilogue.  Y2_DENSE_FUSED=0 runs every pre-activated 1x1 as the two-kernel form instead (y2_preact_fwd + 1x1 y2_conv_fwd): the A/B leg
-of tools/densenet_bench.py.  nn.Conv2d / nn.BatchNorm2d are parameter containers only.
+of tools/densenet_bench.py.  The plan per input shape is built from the shared parts of model/_infer_parts.py (version-keyed prep, y2_conv_params
+filler, zero-filled plan buffers, scratch, forward() dispatch); a new parameter version plans again.  nn.Conv2d / nn.BatchNorm2d are parameter
+containers only.
 
 Training runs through model/train_oplist.py (OpListTrainFn, _build_densenet: 'pre' / 'grow' ops): the batch statistics of a slab of the
 concatenation are taken once, by its producer, and every consumer's BatchNorm finalises from them; the backward walks a block's layers in reverse
@@ -30,16 +32,13 @@ import torch.nn as nn
 
 import model
 import _hip
+from model import _infer_parts as parts
+from model._infer_parts import pad4 as _pad4
 
-BN_EPS = 1e-5
 # How a pre-activated 1x1 convolution runs: True = y2_preact_conv1x1_fwd, False = the two-kernel form (y2_preact_fwd + 1x1 y2_conv_fwd), None = per layer
 # shape whichever measures faster on this device (timed once when the shape is first planned, kept in the tune table like the algorithm choices of
 # _hip.autotune_conv; the fused kernel where nothing can be measured: Y2_AUTOTUNE=0, deterministic mode, during a graph capture).
 FUSED = {'1': True, '0': False}.get(os.environ.get('Y2_DENSE_FUSED', ''))
-
-
-def _pad4(c):
-    return (c + 3) // 4 * 4
 
 
 class _Seq(nn.Sequential):
@@ -75,7 +74,7 @@ class _Transition(_Seq):
         ]))
 
 
-class DenseNet(nn.Module):
+class DenseNet(parts.InferMixin, nn.Module):
     """model/densenet.py:29-65."""
 
     def __init__(self, config_channels, anchors, num_cls, growth_rate=32, block_config=(6, 12, 24, 16), num_init_features=64, bn_size=4, drop_rate=0):
@@ -104,10 +103,7 @@ class DenseNet(nn.Module):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
         self.block_config = tuple(block_config)
-        self._cache = None
-        self._plans = _hip.PlanCache()
-        self.profile = None
-        self.grad_ready_hook = None   # train.DataParallelRCCL: called as hook(param, grad) from inside backward
+        self._init_runtime()
 
     # ---- structure
     def blocks(self):
@@ -115,47 +111,22 @@ class DenseNet(nn.Module):
         n = len(self.block_config)
         return [(getattr(self.features, 'denseblock%d' % (i + 1)), getattr(self.features, 'transition%d' % (i + 1)) if i != n - 1 else None) for i in range(n)]
 
-    @property
-    def _plan_cache(self):
-        """(tools / bench) the most recently used plan as (key, plan), None before the first forward."""
-        plan = self._plans.latest()
-        return None if plan is None else (plan['key'], plan)
-
-    @_plan_cache.setter
-    def _plan_cache(self, value):
-        assert value is None
-        self._plans.clear()
-
     # ------------------------------------------------------------------ preparation: packed weights + folded BN
-    def _versions(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
     def _prepare(self, dev):
+        """prep[bn] = (scale, shift); prep[conv] = (weight as its kernel reads it, Cin as stored, Cout, k); prep['bias'] = the head's."""
         ver = (dev, self._versions())
-        if self._cache is not None and self._cache[0] == ver:
-            return self._cache[1]
+        prep = self._cached_prep(ver)
+        if prep is not None:
+            return prep
         L = _hip.lib()
         st = _hip.stream()
         prep = {}
 
         def fold_bn(bn):
-            c = bn.weight.shape[0]
-            scale, shift = torch.empty(c, device=dev), torch.empty(c, device=dev)
-            _hip.check(L.y2_bn_fold(_hip.ptr(_hip.f32c(bn.weight.detach())), _hip.ptr(_hip.f32c(bn.bias.detach())), _hip.ptr(_hip.f32c(bn.running_mean)),
-                                    _hip.ptr(_hip.f32c(bn.running_var)), BN_EPS, _hip.ptr(scale), _hip.ptr(shift), c, st), 'y2_bn_fold')
-            prep[bn] = (scale, shift)
+            prep[bn] = parts.fold_bn(L, st, dev, bn)
 
         def pack(conv):
-            w = _hip.f32c(conv.weight.detach())
-            _hip.require_gpu(w)
-            cout, cin, k, _ = w.shape
-            if cin % 4:                                   # zero-padded input channels (the 3-channel image, widths that are not multiples of 4)
-                wpad = torch.zeros(cout, _pad4(cin), k, k, dtype=torch.float32, device=dev)
-                wpad[:, :cin] = w
-                w, cin = wpad, wpad.shape[1]
-            wp = torch.empty(w.numel(), dtype=torch.float32, device=dev)
-            _hip.check(L.y2_pack_weight(_hip.ptr(w), _hip.ptr(wp), cout, cin, k, 0, st), 'y2_pack_weight')
-            prep[conv] = (wp, cin, cout, k)
+            prep[conv] = parts.pack_weight(L, st, dev, conv.weight)      # (zero-padded input channels: the 3-channel image, widths that are not multiples of 4)
 
         def plain(conv):
             w = _hip.f32c(conv.weight.detach())           # [N][K][1][1]: read as it is by y2_preact_conv1x1_fwd (and, k = 1, by y2_conv_fwd)
@@ -175,37 +146,26 @@ class DenseNet(nn.Module):
                 plain(trans.conv)
         fold_bn(f.norm5)
         plain(f.conv)
-        prep['bias'] = _hip.f32c(f.conv.bias.detach())
+        prep['bias'] = parts.affine(L, st, dev, f.conv, None)[1]
         self._cache = (ver, prep)
         return prep
 
     def _plan(self, prep, dev, B, cin0, H, W):
-        widths = tuple(tuple(m.weight.shape) for m in self.modules() if isinstance(m, nn.Conv2d))
-        key = (str(dev), B, cin0, H, W, _hip.tune_epoch(), _hip.WINOGRAD, _hip.FORCE_ALGO, FUSED, widths)
+        key = self._plan_key(dev, B, cin0, H, W, FUSED)
         plan = self._plans.get(key)
         if plan is not None and plan['prep'] is prep:
             return plan
         # (a new parameter version re-plans: the buffers of the old plan are dropped with it; the algorithm choices come from the table)
-        nbytes = [0]
-
-        def new(*s):
-            t = torch.zeros(*s, dtype=torch.float32, device=dev)       # zero: the channel padding of an activation stays zero
-            nbytes[0] += t.numel() * 4
-            return t
-        keep, steps, flops, convs = [], [], [0.0], []
+        build = parts.PlanBuilder(dev, torch.zeros)      # zero: the channel padding of an activation stays zero
+        new, keep = build.new, build.keep
+        steps, convs = [], []
         wino = {}
 
         def conv_step(conv, scale, shift, x, h, w, ldx, y, ldy, coff, stride, pad, slope):
             wp, cin, cout, k = prep[conv]
-            p = _hip.ConvParams()
-            p.x, p.w = x.data_ptr(), wp.data_ptr()
-            p.scale = scale.data_ptr() if scale is not None else None
-            p.shift = shift.data_ptr() if shift is not None else None
-            p.y, p.ldy, p.coff = y.data_ptr(), ldy, coff
-            p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, h, w, cin, ldx, cout, k
-            p.stride, p.pad_plus1, p.slope, p.tile = stride, pad + 1, slope, 0
-            ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-            flops[0] += 2.0 * conv.weight.shape[1] * cout * k * k * B * ho * wo
+            p, f = parts.conv_params(x, wp, scale, shift, B, h, w, cin, ldx, cout, k, slope, y=y, ldy=ldy, coff=coff, stride=stride, pad=pad,
+                                     real_cin=conv.weight.shape[1])
+            build.flops += f
             u = None
             if _hip.wino_eligible(cout, cin, k, stride) and pad == 1:
                 u = wino[id(p)] = _hip.wino_weight(wp, cout, cin)
@@ -217,13 +177,7 @@ class DenseNet(nn.Module):
             wt, _, N, _ = prep[conv]
             ho, wo = (h // 2, w // 2) if pool else (h, w)
             act = torch.empty(B, ho, wo, K, dtype=torch.float32, device=dev)
-            p = _hip.ConvParams()
-            p.x, p.w = act.data_ptr(), wt.data_ptr()
-            p.scale = scale.data_ptr() if scale is not None else None
-            p.shift = shift.data_ptr() if shift is not None else None
-            p.y, p.ldy, p.coff = y.data_ptr(), ldy, coff
-            p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, ho, wo, K, K, N, 1
-            p.stride, p.pad_plus1, p.slope, p.tile = 1, 1, slope, 0
+            p, _ = parts.conv_params(act, wt, scale, shift, B, ho, wo, K, K, N, 1, slope, y=y, ldy=ldy, coff=coff, stride=1, pad=0)
             _hip.autotune_conv(p, dev)
             _hip.conv_workspace(p, dev)
             return act, p, [('act', x, pre[0], pre[1], pre_slope, act, h, w, K, ldx, pool), ('conv', p)]
@@ -232,7 +186,7 @@ class DenseNet(nn.Module):
             wt, cin, N, _ = prep[conv]
             assert cin == K
             ho, wo = (h // 2, w // 2) if pool else (h, w)
-            flops[0] += 2.0 * K * N * B * ho * wo
+            build.flops += 2.0 * K * N * B * ho * wo
             fused_step = ('pre', x, wt, pre[0], pre[1], pre_slope, scale, shift, slope, y, h, w, K, ldx, N, ldy, coff, pool)
             args = (conv, pre, pre_slope, scale, shift, slope, x, h, w, K, ldx, y, ldy, coff, pool)
             fused = FUSED
@@ -257,7 +211,7 @@ class DenseNet(nn.Module):
                 steps.append(fused_step)
                 return
             act, p, pair = pair if pair is not None else two_kernel(*args)
-            nbytes[0] += act.numel() * 4
+            build.nbytes += act.numel() * 4
             keep.append(act)
             convs.append(p)
             steps.extend(pair)
@@ -268,14 +222,12 @@ class DenseNet(nn.Module):
         c0 = f.conv0.weight.shape[0]
         h1, w1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         stem = new(B, h1, w1, _pad4(c0))
-        keep += [x4, stem]
         conv_step(f.conv0, prep[f.norm0][0], prep[f.norm0][1], x4, H, W, cpad, stem, _pad4(c0), 0, 2, 3, 0.0)
         h, w = (h1 + 2 - 3) // 2 + 1, (w1 + 2 - 3) // 2 + 1
         c, buf = c0, None
         for bi, (block, trans) in enumerate(self.blocks()):
             c_end = c + sum(layer.conv2.weight.shape[0] for layer in block)
             nxt = new(B, h, w, c_end)
-            keep.append(nxt)
             if bi == 0:
                 steps.append(('maxpool', stem, nxt, h1, w1, c0, _pad4(c0), c_end))
             else:
@@ -285,7 +237,6 @@ class DenseNet(nn.Module):
             for layer in block:
                 n1 = layer.conv1.weight.shape[0]
                 tmp = new(B, h, w, _pad4(n1))
-                keep.append(tmp)
                 preact_step(layer.conv1, prep[layer.norm1], 0.0, prep[layer.norm2][0], prep[layer.norm2][1], 0.0, buf, h, w, c, c_end, tmp, _pad4(n1), 0, 0)
                 conv_step(layer.conv2, None, None, tmp, h, w, _pad4(n1), buf, c_end, c, 1, 1, 1.0)
                 c += layer.conv2.weight.shape[0]
@@ -297,14 +248,10 @@ class DenseNet(nn.Module):
         head = f.conv
         head_shape = (B, h, w, head.weight.shape[0])
         head_y = new(*head_shape)          # (what the timing runs of the head write; forward_nhwc binds a fresh output per call)
-        keep.append(head_y)
         preact_step(head, prep[f.norm5], 1.0, None, prep['bias'], 1.0, buf, h, w, c, c, head_y, head.weight.shape[0], 0, 0)
-        need = max([_hip.lib().y2_conv_fwd_workspace_bytes(ctypes.byref(p)) for p in convs] + [0])
-        ws = _hip.workspace(dev, need) if need > 0 else None
-        for p in convs:
-            p.workspace, p.workspace_bytes = (ws.data_ptr(), ws.numel() * 4) if ws is not None else (None, 0)
-        plan = dict(key=key, x4=x4, cpad=cpad, steps=steps, head_shape=head_shape, flops=flops[0], prep=prep, keep=(keep, ws, wino))
-        self._plans.put(key, plan, nbytes[0])
+        ws = build.share_workspace(convs)
+        plan = dict(key=key, x4=x4, cpad=cpad, steps=steps, head_shape=head_shape, flops=build.flops, prep=prep, keep=(keep, ws, wino))
+        self._plans.put(key, plan, build.nbytes)
         return plan
 
     @staticmethod
@@ -346,39 +293,21 @@ class DenseNet(nn.Module):
         return sorted(times)[len(times) // 2]
 
     def forward_nhwc(self, x):
-        _hip.require_gpu(x)
+        x, B, cin0, H, W, dev = parts.enter(x)
         L = _hip.lib()
-        x = _hip.f32c(x)
-        B, cin0, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError('input size must be a multiple of 32 (got %dx%d)' % (H, W))
-        dev = x.device
         prep = self._prepare(dev)
         plan = self._plan(prep, dev, B, cin0, H, W)
         st = _hip.stream()
         out = torch.empty(plan['head_shape'], dtype=torch.float32, device=dev)
-        prof = self.profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = parts.profile_begin(self)
         _hip.check(L.y2_nchw_to_nhwc(_hip.ptr(x), _hip.ptr(plan['x4']), B, cin0, H, W, plan['cpad'], st), 'y2_nchw_to_nhwc')
         self._run(plan['steps'], B, st, out)
-        if prof is not None:
-            e1.record()
-            prof.append(('conv_fwd', plan['flops'], e0, e1))
+        parts.profile_end(self, e0, plan['flops'])
         return out
 
     def forward(self, x):
         _hip.require_gpu(x)
-        if self.training:        # BN semantics follow self.training alone (see model.yolo2.Darknet.forward)
-            from model import train_oplist
-            return train_oplist.forward(self, x)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_oplist
-            return train_oplist.forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
-        with torch.no_grad():
-            out = self.forward_nhwc(x)
-        return out.permute(0, 3, 1, 2)
+        return parts.InferMixin.forward(self, x)
 
     def backward_param_order(self):
         """Convolution weights in the order the training backward finishes their gradients (the reverse of the forward's op list)."""
@@ -396,13 +325,7 @@ class DenseNet(nn.Module):
 def _make(**arch):
     def ctor(config_channels, anchors, num_cls, **kwargs):
         net = DenseNet(config_channels, anchors, num_cls, **dict(arch, **kwargs))
-        try:
-            pretrained = config_channels.config.getboolean('model', 'pretrained')
-        except Exception:
-            pretrained = False
-        if pretrained:   # model/densenet.py:70-77 loads the torchvision model-zoo weights by URL
-            raise RuntimeError('model.densenet: [model] pretrained=1 cannot be honoured (no torchvision model zoo / network here); '
-                               'set pretrained=0 and load a checkpoint with load_state_dict (same keys as torchvision.models.densenet)')
+        parts.refuse_pretrained(config_channels, 'model.densenet')      # model/densenet.py:70-77
         return net
     return ctor
 

@@ -10,7 +10,9 @@ Execution (inference): the NCHW input is converted once to zero-padded 4-channel
 1x1 pointwise convolution are y2_conv_fwd launches with BatchNorm folded into the epilogue and ReLU as LeakyReLU(slope 0); every
 depthwise 3x3 is one y2_dwconv_fwd launch (csrc/dwconv.hip) with its folded BatchNorm and ReLU in the epilogue; the head is a 1x1
 y2_conv_fwd with its bias.  Activations carry a pixel stride rounded up to 4 channels (zero padding), so pruned odd widths run in
-inference (the depthwise kernel then takes its scalar path).  nn.Conv2d / nn.BatchNorm2d are parameter containers only.  Training
+inference (the depthwise kernel then takes its scalar path).  The plan per input shape is built from the shared parts of model/_infer_parts.py
+(version-keyed prep, y2_conv_params filler, zero-filled plan buffers, scratch, pointer rebinding, forward() dispatch).  nn.Conv2d /
+nn.BatchNorm2d are parameter containers only.  Training
 runs through model/train_oplist.py (OpListTrainFn, _build_mobilenet: batch-statistics BN, depthwise data / weight gradients by
 y2_dwconv_dgrad / y2_dwconv_wgrad); it needs every width to be a multiple of 4.
 """
@@ -22,14 +24,10 @@ import torch.nn as nn
 
 import model
 import _hip
-
-BN_EPS = 1e-5
+from model import _infer_parts as parts
+from model._infer_parts import pad4 as _pad4
 STRIDES = (1, 2, 1, 2, 1, 2, 1, 1, 1, 1, 1, 2, 1)                      # layers.1 .. layers.13 (model/mobilenet.py:58-70)
 WIDTHS = (64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024)
-
-
-def _pad4(c):
-    return (c + 3) // 4 * 4
 
 
 class _Seq(nn.Sequential):
@@ -68,7 +66,7 @@ def conv_unit(in_channels, out_channels, stride):
     ]))
 
 
-class MobileNet(nn.Module):
+class MobileNet(parts.InferMixin, nn.Module):
     """model/mobilenet.py:54-85."""
 
     def __init__(self, config_channels, anchors, num_cls):
@@ -84,10 +82,7 @@ class MobileNet(nn.Module):
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
-        self._cache = None
-        self._plans = _hip.PlanCache()
-        self.profile = None
-        self.grad_ready_hook = None   # train.DataParallelRCCL: called as hook(param, grad) from inside backward
+        self._init_runtime()
 
     # ---- structure
     def stem(self):
@@ -109,56 +104,25 @@ class MobileNet(nn.Module):
         fwd.append(self.head())
         return [c.weight for c in reversed(fwd)]
 
-    @property
-    def _plan_cache(self):
-        """(tools / bench) the most recently used plan as (key, plan), None before the first forward."""
-        plan = self._plans.latest()
-        return None if plan is None else (plan['key'], plan)
-
-    @_plan_cache.setter
-    def _plan_cache(self, value):
-        assert value is None
-        self._plans.clear()
-
     # ------------------------------------------------------------------ preparation: packed weights + folded BN
-    def _versions(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
     def _prepare(self, dev):
+        """prep[conv] = (wp, scale, shift, Cin as packed, Cout, k); of a depthwise convolution (w, scale, shift)."""
         ver = (dev, self._versions())
-        if self._cache is not None and self._cache[0] == ver:
-            return self._cache[1]
+        prep = self._cached_prep(ver)
+        if prep is not None:
+            return prep
         L = _hip.lib()
         st = _hip.stream()
         prep = {}
 
-        def affine(conv, bn):
-            cout = conv.weight.shape[0]
-            if bn is None:
-                return None, (_hip.f32c(conv.bias.detach()) if conv.bias is not None else None)
-            scale, shift = torch.empty(cout, device=dev), torch.empty(cout, device=dev)
-            _hip.check(L.y2_bn_fold(_hip.ptr(_hip.f32c(bn.weight.detach())), _hip.ptr(_hip.f32c(bn.bias.detach())), _hip.ptr(_hip.f32c(bn.running_mean)),
-                                    _hip.ptr(_hip.f32c(bn.running_var)), BN_EPS, _hip.ptr(scale), _hip.ptr(shift), cout, st), 'y2_bn_fold')
-            return scale, shift
-
         def fold(conv, bn):
-            w = _hip.f32c(conv.weight.detach())
-            _hip.require_gpu(w)
-            cout, cin, k, _ = w.shape
-            if cin % 4:                                   # zero-padded input channels (the 3-channel image, pruned widths)
-                wpad = torch.zeros(cout, _pad4(cin), k, k, dtype=torch.float32, device=dev)
-                wpad[:, :cin] = w
-                w, cin = wpad, wpad.shape[1]
-            wp = torch.empty(w.numel(), dtype=torch.float32, device=dev)
-            _hip.check(L.y2_pack_weight(_hip.ptr(w), _hip.ptr(wp), cout, cin, k, 0, st), 'y2_pack_weight')
-            scale, shift = affine(conv, bn)
-            prep[conv] = (wp, scale, shift, cin, cout, k)
+            wp, cin, cout, k = parts.pack_weight(L, st, dev, conv.weight)      # (zero-padded input channels: the 3-channel image, pruned widths)
+            prep[conv] = (wp,) + parts.affine(L, st, dev, conv, bn) + (cin, cout, k)
 
         def fold_dw(conv, bn):
             w = _hip.f32c(conv.weight.detach())           # [C][1][3][3]: read as it is by y2_dwconv_fwd
             _hip.require_gpu(w)
-            scale, shift = affine(conv, bn)
-            prep[conv] = (w, scale, shift)
+            prep[conv] = (w,) + parts.affine(L, st, dev, conv, bn)
         fold(self.stem().conv, self.stem().bn)
         for _, unit, _ in self.units():
             fold_dw(unit.dw.conv, unit.dw.bn)
@@ -168,63 +132,43 @@ class MobileNet(nn.Module):
         return prep
 
     def _plan(self, prep, dev, B, cin0, H, W):
-        widths = tuple(tuple(m.weight.shape) for m in self.modules() if isinstance(m, nn.Conv2d))      # (pruned / replaced layers re-plan)
-        key = (str(dev), B, cin0, H, W, _hip.tune_epoch(), _hip.WINOGRAD, _hip.FORCE_ALGO, widths)
+        key = self._plan_key(dev, B, cin0, H, W)
         plan = self._plans.get(key)
         if plan is not None:
-            if plan['prep'] is not prep:      # same shape, new parameter version: only the weight / affine pointers move
+            if plan['prep'] is not prep:
                 for step in plan['steps']:
                     if step[0] == 'conv':
-                        p, conv = step[1], step[2]
-                        wp, scale, shift = prep[conv][:3]
-                        p.w = wp.data_ptr()
-                        p.scale = scale.data_ptr() if scale is not None else None
-                        p.shift = shift.data_ptr() if shift is not None else None
+                        parts.PlanBuilder.rebind(step[1], *prep[step[2]][:3])
                     else:
                         step[2] = prep[step[1]]
                 plan['prep'] = prep
             return plan
-        nbytes = [0]
-
-        def new(*s):
-            t = torch.zeros(*s, dtype=torch.float32, device=dev)       # zero: the channel padding of every activation stays zero
-            nbytes[0] += t.numel() * 4
-            return t
-        keep, steps, flops = [], [], [0.0]
+        build = parts.PlanBuilder(dev, torch.zeros)      # zero: the channel padding of every activation stays zero
+        new = build.new
+        steps = []
 
         def conv_step(conv, x, h, w, ldx, y, ldy, stride, pad, slope):
             wp, scale, shift, cin, cout, k = prep[conv]
-            p = _hip.ConvParams()
-            p.x, p.w = x.data_ptr(), wp.data_ptr()
-            p.scale = scale.data_ptr() if scale is not None else None
-            p.shift = shift.data_ptr() if shift is not None else None
-            p.y, p.ldy = y.data_ptr(), ldy
-            p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, h, w, cin, ldx, cout, k
-            p.stride, p.pad_plus1, p.slope, p.tile = stride, pad + 1, slope, 0
-            ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-            flops[0] += 2.0 * conv.weight.shape[1] * cout * k * k * B * ho * wo
+            p, f = parts.conv_params(x, wp, scale, shift, B, h, w, cin, ldx, cout, k, slope, y=y, ldy=ldy, stride=stride, pad=pad,
+                                     real_cin=conv.weight.shape[1])
+            build.flops += f
             steps.append(['conv', p, conv])
-            return ho, wo
 
         cpad = _pad4(cin0)
         x4 = new(B, H, W, cpad)
-        keep.append(x4)
         c = self.stem().conv.weight.shape[0]
         ld = _pad4(c)
         h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         cur = new(B, h, w, ld)
-        keep.append(cur)
         conv_step(self.stem().conv, x4, H, W, cpad, cur, ld, 2, 1, 0.0)
         for _, unit, s in self.units():
             ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
             d = new(B, ho, wo, ld)
-            keep.append(d)
             steps.append(['dw', unit.dw.conv, prep[unit.dw.conv], cur, d, B, h, w, c, ld, ld, s])
-            flops[0] += 2.0 * 9 * B * ho * wo * c
+            build.flops += 2.0 * 9 * B * ho * wo * c
             co = unit.pw.conv.weight.shape[0]
             ldo = _pad4(co)
             y = new(B, ho, wo, ldo)
-            keep.append(y)
             conv_step(unit.pw.conv, d, ho, wo, ld, y, ldo, 1, 0, 0.0)
             cur, h, w, c, ld = y, ho, wo, co, ldo
         head = self.head()
@@ -235,31 +179,20 @@ class MobileNet(nn.Module):
         for p in convs:
             if p is not head_p:
                 _hip.autotune_conv(p, dev)
-        need = max([_hip.lib().y2_conv_fwd_workspace_bytes(ctypes.byref(p)) for p in convs] + [0])
-        ws = _hip.workspace(dev, need) if need > 0 else None
-        for p in convs:
-            p.workspace, p.workspace_bytes = (ws.data_ptr(), ws.numel() * 4) if ws is not None else (None, 0)
-        plan = dict(key=key, x4=x4, cpad=cpad, steps=steps, head=head_p, head_shape=head_shape, flops=flops[0], prep=prep, keep=(keep, ws))
-        self._plans.put(key, plan, nbytes[0])
+        ws = build.share_workspace(convs)
+        plan = dict(key=key, x4=x4, cpad=cpad, steps=steps, head=head_p, head_shape=head_shape, flops=build.flops, prep=prep, keep=(build.keep, ws))
+        self._plans.put(key, plan, build.nbytes)
         return plan
 
     def forward_nhwc(self, x):
-        _hip.require_gpu(x)
+        x, B, cin0, H, W, dev = parts.enter(x)
         L = _hip.lib()
-        x = _hip.f32c(x)
-        B, cin0, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError('input size must be a multiple of 32 (got %dx%d)' % (H, W))
-        dev = x.device
         prep = self._prepare(dev)
         plan = self._plan(prep, dev, B, cin0, H, W)
         st = _hip.stream()
         out = torch.empty(plan['head_shape'], dtype=torch.float32, device=dev)
         plan['head'].y = out.data_ptr()
-        prof = self.profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = parts.profile_begin(self)
         _hip.check(L.y2_nchw_to_nhwc(_hip.ptr(x), _hip.ptr(plan['x4']), B, cin0, H, W, plan['cpad'], st), 'y2_nchw_to_nhwc')
         for step in plan['steps']:
             if step[0] == 'conv':
@@ -268,18 +201,5 @@ class MobileNet(nn.Module):
                 _, _, (wt, scale, shift), xin, y, b, h, w, c, ldx, ldy, s = step
                 _hip.check(L.y2_dwconv_fwd(_hip.ptr(xin), _hip.ptr(wt), _hip.ptr(scale), _hip.ptr(shift), 0.0, _hip.ptr(y), None,
                                            b, h, w, c, ldx, ldy, s, st), 'y2_dwconv_fwd')
-        if prof is not None:
-            e1.record()
-            prof.append(('conv_fwd', plan['flops'], e0, e1))
+        parts.profile_end(self, e0, plan['flops'])
         return out
-
-    def forward(self, x):
-        if self.training:        # BN semantics follow self.training alone (see model.yolo2.Darknet.forward)
-            from model import train_oplist
-            return train_oplist.forward(self, x)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_oplist
-            return train_oplist.forward(self, x, frozen=True)     # differentiable eval mode: frozen BatchNorm statistics
-        with torch.no_grad():
-            out = self.forward_nhwc(x)
-        return out.permute(0, 3, 1, 2)

@@ -3,7 +3,9 @@
 forward(net, x) records the network as a list of operations while it launches them - a builder function per architecture drives a
 _Recorder, whose conv_bn / dwconv_bn / maxpool methods launch one operation each and note what its backward needs - and
 OpListTrainFn.backward walks that list in reverse with gradient fan-in per tensor.  A new backbone is a builder over the recorder
-(and an entry in _builder); the parts shared with the Darknet graph of model/train_graph.py live in model/_train_parts.py."""
+(and an entry in _builder); the parts shared with the Darknet graph of model/train_graph.py live in model/_train_parts.py.  For inference
+the same backbone writes a class on model/_infer_parts.InferMixin with its own _prepare (pack_weight / fold_bn per layer), _plan (a walk that
+fills conv_params into a PlanBuilder) and forward_nhwc (enter, the launches)."""
 import torch
 
 import _hip

@@ -15,6 +15,9 @@ convolution.  nn.Conv2d / nn.BatchNorm2d objects below are PARAMETER
 CONTAINERS only (their forward is never called); the constructor is CPU-only
 and lazy (no HIP call until a GPU tensor reaches forward), as required by the
 reference's fork-after-init SummaryWorker (train.py:278-279).
+
+Execution (inference): Darknet._plan walks the architecture once per input shape; the version-keyed prep, the y2_conv_params filler, the plan's
+buffers and scratch and the forward() dispatch are the shared parts of model/_infer_parts.py.  Tiny runs the same kernels without a plan.
 """
 import ctypes
 
@@ -23,13 +26,12 @@ import torch.nn as nn
 
 import model
 import _hip
+from model import _infer_parts as parts
+from model._infer_parts import LEAKY
 
 settings = {
     'size': (416, 416),
 }
-
-BN_EPS = 1e-5
-LEAKY = 0.1
 
 
 class Conv2d(nn.Module):
@@ -92,7 +94,7 @@ def _init_reference(net, conv_init):
             nn.init.zeros_(m.bias)
 
 
-class Darknet(nn.Module):
+class Darknet(parts.InferMixin, nn.Module):
     def __init__(self, config_channels, anchors, num_cls, stride=2, ratio=1):
         nn.Module.__init__(self)
         if stride != 2:
@@ -111,10 +113,7 @@ class Darknet(nn.Module):
         self.layers3 = nn.Sequential(Conv2d(c_cat, c_mix, 3, bn=bn, padding=True),
                                      Conv2d(c_mix, model.output_channels(len(anchors), num_cls), 1, bn=False, act=False))
         self.init()
-        self._cache = None  # packed weights / folded BN for eval, keyed on parameter versions
-        self._plans = _hip.PlanCache()  # execution plans (intermediate buffers + y2_conv_params arrays) per input shape, LRU
-        self.grad_ready_hook = None  # set by train.DataParallelRCCL: called as hook(param, grad) inside backward, layer by layer
-        self.profile = None  # tools: list receiving (kernel, flops, start_event, end_event) per conv launch
+        self._init_runtime()
 
     def init(self):
         _init_reference(self, nn.init.kaiming_normal_)
@@ -152,33 +151,17 @@ class Darknet(nn.Module):
         fwd = [m for _, m, _ in b1] + [self.passthrough] + [m for _, m, _ in b2] + [m for _, m, _ in b3]
         return [m.conv.weight for m in reversed(fwd)]
 
-    def _versions(self):
-        """Cache key of everything derived from the parameters and buffers: (address, torch version counter) per tensor.  The
-        raw-pointer writers (utils.optim, y2_bn_finalize) advance the counters of what they wrote through _hip.wrote, so the key is
-        per tensor and per model: training another model does not touch it."""
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
     def _weight_versions(self):
         """Cache key of what is derived from the convolution weights alone (the training step's GEMM operands): BatchNorm buffer
         updates of a forward pass do not move it."""
         return tuple((m.conv.weight.data_ptr(), m.conv.weight._version) for m in self.modules() if isinstance(m, Conv2d))
 
-    @property
-    def _plan_cache(self):
-        """(tools / bench) the most recently used plan as (key, plan), None before the first forward."""
-        plan = self._plans.latest()
-        return None if plan is None else (plan['key'], plan)
-
-    @_plan_cache.setter
-    def _plan_cache(self, value):
-        assert value is None
-        self._plans.clear()
-
     def _prepare_eval(self, device):
-        """Pack weights to [Cout][tap][Cin] and fold BN once per parameter version (y2_pack_weight / y2_bn_fold)."""
+        """Pack weights to [Cout][tap][Cin] and fold BN once per parameter version (prep[blk] = (wp, scale, shift, Winograd copy or None))."""
         ver = (device, self._versions(), _hip.split_mode())
-        if self._cache is not None and self._cache[0] == ver:
-            return self._cache[1]
+        prep = self._cached_prep(ver)
+        if prep is not None:
+            return prep
         L = _hip.lib()
         st = _hip.stream()
         prep = {}
@@ -187,22 +170,9 @@ class Darknet(nn.Module):
             w = blk.conv.weight.detach()
             _hip.require_gpu(w)
             cout, cin, k, _ = w.shape
-            w = _hip.f32c(w)
-            if blk is first:
-                wp = w  # y2_conv0_fwd reads the state_dict layout directly
-            else:
-                wp = torch.empty(cout * cin * k * k, dtype=torch.float32, device=device)
-                _hip.check(L.y2_pack_weight(_hip.ptr(w), _hip.ptr(wp), cout, cin, k, 0, st), 'y2_pack_weight')
-            if blk.bn is not None:
-                scale = torch.empty(cout, dtype=torch.float32, device=device)
-                shift = torch.empty(cout, dtype=torch.float32, device=device)
-                bn = blk.bn
-                _hip.check(L.y2_bn_fold(_hip.ptr(_hip.f32c(bn.weight.detach())), _hip.ptr(_hip.f32c(bn.bias.detach())),
-                                        _hip.ptr(_hip.f32c(bn.running_mean)), _hip.ptr(_hip.f32c(bn.running_var)),
-                                        BN_EPS, _hip.ptr(scale), _hip.ptr(shift), cout, st), 'y2_bn_fold')
-            else:
-                scale = None
-                shift = _hip.f32c(blk.conv.bias.detach()) if blk.conv.bias is not None else None
+            # y2_conv0_fwd reads the state_dict layout directly; the other layers are packed as they are (no channel padding)
+            wp = _hip.f32c(w) if blk is first else parts.pack_weight(L, st, device, w, pad=False)[0]
+            scale, shift = parts.affine(L, st, device, blk.conv, blk.bn)
             # Winograd-transformed copy of the deep 3x3 filters (the plan picks direct or Winograd per layer by measurement)
             u = _hip.wino_weight(wp, cout, cin) if (blk is not first and _hip.wino_eligible(cout, cin, k)) else None
             prep[blk] = (wp, scale, shift, u)
@@ -211,58 +181,36 @@ class Darknet(nn.Module):
         self._cache = (ver, prep)
         return prep
 
-    def _conv_params(self, prep, blk, x, B, H, W, ldx, y=None, y_pool=None, ldy=0, coff=0, ldp=0, poff=0, out_mode=0):
+    def _conv_params(self, prep, blk, x, B, H, W, ldx, **out):
+        """y2_conv_params of one block (stride and padding stay unset: parts.conv_params) and its multiply-add count."""
         wp, scale, shift, _ = prep[blk]
         cout, cin = blk.conv.weight.shape[:2]
-        p = _hip.ConvParams()
-        p.x, p.w, p.scale, p.shift = x.data_ptr(), wp.data_ptr(), (scale.data_ptr() if scale is not None else None), (shift.data_ptr() if shift is not None else None)
-        p.y = y.data_ptr() if y is not None else None
-        p.y_pool = y_pool.data_ptr() if y_pool is not None else None
-        p.stats = None
-        p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize = B, H, W, cin, ldx, cout, blk.kernel_size
-        p.ldy, p.coff, p.ldp, p.poff, p.out_mode = ldy, coff, ldp, poff, out_mode
-        p.slope = LEAKY if blk.has_act else 1.0
-        p.tile = 0
-        return p, 2.0 * cin * cout * blk.kernel_size ** 2 * B * H * W
+        return parts.conv_params(x, wp, scale, shift, B, H, W, cin, ldx, cout, blk.kernel_size, LEAKY if blk.has_act else 1.0, **out)
 
     def _plan(self, prep, dev, B, cin0, H, W, slot=0):
         """Execution plan for one input shape: intermediate NHWC buffers (never exposed, reused across calls) and the
         y2_conv_params array of the 22 generic convolutions (model/yolo2.py:76-113 in execution order)."""
         # slot: plans of the same shape with PRIVATE intermediate buffers and scratch, so that two batches can be in flight on two streams
         # (detect.GraphedDetector(slot=...): the tail of one batch's kernels overlaps the head of the next batch's)
-        # (the widths are part of the key: a plan's buffers, leading dimensions and algorithm choices are sized for the conv weights it was
-        # built for - channel surgery, a replaced head - while a new parameter VERSION of the same shapes only moves operand pointers)
-        widths = tuple(tuple(m.conv.weight.shape) for m in self.modules() if isinstance(m, Conv2d))
-        key = (str(dev), B, cin0, H, W, _hip.tune_epoch(), _hip.WINOGRAD, _hip.FORCE_ALGO, _hip.split_mode(), slot, widths)
+        key = self._plan_key(dev, B, cin0, H, W, _hip.split_mode(), slot)
         plan = self._plans.get(key)
         if plan is not None:
-            if plan['prep'] is not prep:
-                # same shape, new parameter version (a training step ran in between): the buffers, algorithms and tiles stay, only the
-                # operand pointers of the packed / folded / transformed weights move
+            if plan['prep'] is not prep:      # a training step ran in between
                 for p, blk in zip(plan['arr'], plan['blks']):
                     wp, scale, shift, u = prep[blk]
-                    p.w = (prep['split'][blk] if p.algo in (4, 5) else u if p.algo in (1, 2, 3) else wp).data_ptr()
-                    p.scale = scale.data_ptr() if scale is not None else None
-                    p.shift = shift.data_ptr() if shift is not None else None
+                    parts.PlanBuilder.rebind(p, prep['split'][blk] if p.algo in (4, 5) else u if p.algo in (1, 2, 3) else wp, scale, shift)
                 plan['prep'] = prep
             return plan
-        nbytes = [0]
-
-        def new(*s):
-            t = torch.empty(*s, dtype=torch.float32, device=dev)
-            nbytes[0] += t.numel() * 4
-            return t
+        build = parts.PlanBuilder(dev)
+        new = build.new
         b1, b2, b3 = self._blocks()
-        plist, flops, keep = [], 0.0, []
-
-        ulist, blks = [], []
+        plist, blks = [], []
 
         def add(blk, *args, **kw):
             p, f = self._conv_params(prep, blk, *args, **kw)
             plist.append(p)
-            ulist.append(prep[blk][3])
             blks.append(blk)
-            return f
+            build.flops += f
         name, blk0, pool = b1[0]
         c = blk0.conv.weight.shape[0]
         assert pool
@@ -275,75 +223,61 @@ class Darknet(nn.Module):
                 # output feeds both the passthrough (full res) and layers2's leading MaxPool (model/yolo2.py:97,126-128)
                 full_last = new(B, h, w, c)
                 pooled = new(B, h // 2, w // 2, c)
-                flops += add(blk, cur, B, h, w, ld, y=full_last, y_pool=pooled, ldy=c, ldp=c)
+                add(blk, cur, B, h, w, ld, y=full_last, y_pool=pooled, ldy=c, ldp=c)
                 cur, fh, fw = pooled, h, w
                 h, w, ld = h // 2, w // 2, c
             elif pool:
                 out = new(B, h // 2, w // 2, c)
-                flops += add(blk, cur, B, h, w, ld, y_pool=out, ldp=c)
+                add(blk, cur, B, h, w, ld, y_pool=out, ldp=c)
                 cur, h, w, ld = out, h // 2, w // 2, c
             else:
                 out = new(B, h, w, c)
-                flops += add(blk, cur, B, h, w, ld, y=out, ldy=c)
+                add(blk, cur, B, h, w, ld, y=out, ldy=c)
                 cur, ld = out, c
-            keep.append(cur)
         # concat buffer [B, h, w, 4*c_pt + c_l2]; the passthrough writes its reorg'ed channels FIRST (model/yolo2.py:129)
         c_pt = self.passthrough.conv.weight.shape[0]
         c_l2 = b2[-1][1].conv.weight.shape[0]
         cat = new(B, h, w, 4 * c_pt + c_l2)
-        flops += add(self.passthrough, full_last, B, fh, fw, full_last.shape[-1], y=cat, ldy=cat.shape[-1], coff=0, out_mode=1)
+        add(self.passthrough, full_last, B, fh, fw, full_last.shape[-1], y=cat, ldy=cat.shape[-1], coff=0, out_mode=1)
         for i, (name, blk, pool) in enumerate(b2):
             c = blk.conv.weight.shape[0]
             if i == len(b2) - 1:
-                flops += add(blk, cur, B, h, w, ld, y=cat, ldy=cat.shape[-1], coff=4 * c_pt)
+                add(blk, cur, B, h, w, ld, y=cat, ldy=cat.shape[-1], coff=4 * c_pt)
             else:
                 out = new(B, h, w, c)
-                flops += add(blk, cur, B, h, w, ld, y=out, ldy=c)
+                add(blk, cur, B, h, w, ld, y=out, ldy=c)
                 cur, ld = out, c
-                keep.append(out)
         cur, ld = cat, cat.shape[-1]
         head_index = None
         for i, (name, blk, pool) in enumerate(b3):
             c = blk.conv.weight.shape[0]
             if i == len(b3) - 1:
                 head_index = len(plist)          # output buffer is allocated per call (it is returned to the caller)
-                flops += add(blk, cur, B, h, w, ld, y=cur, ldy=c)
+                add(blk, cur, B, h, w, ld, y=cur, ldy=c)
                 head_shape = (B, h, w, c)
             else:
                 out = new(B, h, w, c)
-                flops += add(blk, cur, B, h, w, ld, y=out, ldy=c)
+                add(blk, cur, B, h, w, ld, y=out, ldy=c)
                 cur, ld = out, c
-                keep.append(out)
-        for p, u, blk in zip(plist, ulist, blks):
-            _hip.autotune_conv(p, dev, wino_w=u, wino_split=prep.get('split', {}).get(blk))      # per-layer algorithm + tile choice by measurement (cached per problem shape)
-        need = max([_hip.lib().y2_conv_fwd_workspace_bytes(ctypes.byref(p)) for p in plist] + [0])
-        if slot == 0:
-            ws = _hip.workspace(dev, need) if need > 0 else None
-        else:
-            ws = new(int(need) // 4 + 4) if need > 0 else None      # (the per-device scratch is shared by everything that runs on ONE stream)
-        for p in plist:
-            p.workspace, p.workspace_bytes = (ws.data_ptr(), ws.numel() * 4) if ws is not None else (None, 0)
+        for p, blk in zip(plist, blks):
+            _hip.autotune_conv(p, dev, wino_w=prep[blk][3], wino_split=prep.get('split', {}).get(blk))      # per-layer algorithm + tile choice by measurement (cached per problem shape)
+        ws = build.share_workspace(plist, private=slot != 0)      # (the per-device scratch is shared by everything that runs on ONE stream)
         arr = (_hip.ConvParams * len(plist))(*plist)
         # multiply-adds the MFMA pipe really executes: a Winograd layer runs 16 GEMMs over ceil(H/2)*ceil(W/2) tiles per image
         executed = sum(2.0 * p.Cin * p.Cout * (16 * p.B * ((p.H + 1) // 2) * ((p.W + 1) // 2) if p.algo in (1, 2, 3, 4, 5) else p.ksize ** 2 * p.B * p.H * p.W)
                        for p in plist)
-        plan = dict(key=key, arr=arr, n=len(plist), first=first, head_index=head_index, head_shape=head_shape, flops=flops, flops_executed=executed,
+        plan = dict(key=key, arr=arr, n=len(plist), first=first, head_index=head_index, head_shape=head_shape, flops=build.flops, flops_executed=executed,
                     algos=[int(p.algo != 0) for p in plist], blks=blks, prep=prep,
-                    flops0=2.0 * cin0 * blk0.conv.weight.shape[0] * 9 * B * H * W, keep=(keep, full_last, cat, ws))
-        self._plans.put(key, plan, nbytes[0])
+                    flops0=2.0 * cin0 * blk0.conv.weight.shape[0] * 9 * B * H * W, keep=(build.keep, ws))
+        self._plans.put(key, plan, build.nbytes)
         return plan
 
     def forward_nhwc(self, x, slot=0):
         """x [B,Cin,H,W] NCHW fp32 on the GPU -> head image [B, H/32, W/32, A*(5+C)] (NHWC, contiguous).
         Inference path (folded BatchNorm): one y2_conv0_fwd + one y2_conv_fwd_batch call.  `slot`: which private set of intermediate
         buffers to run in (calls that may overlap on different streams must use different slots)."""
-        _hip.require_gpu(x)
+        x, B, cin0, H, W, dev = parts.enter(x)
         L = _hip.lib()
-        x = _hip.f32c(x)
-        B, cin0, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError('input size must be a multiple of 32 (got %dx%d)' % (H, W))
-        dev = x.device
         prep = self._prepare_eval(dev)
         plan = self._plan(prep, dev, B, cin0, H, W, slot)
         st = _hip.stream()
@@ -367,23 +301,9 @@ class Darknet(nn.Module):
             prof.append(('conv_fwd', plan['flops'], ev[1], ev[2], plan['flops_executed'], sum(plan['algos'])))
         return out
 
-    def forward(self, x):
-        # BN semantics follow self.training alone, like nn.BatchNorm2d (model/yolo2.py:58): train() mode normalises with batch
-        # statistics and updates the running ones whether or not autograd is recording (under no_grad the graph is simply
-        # not taped); eval() mode runs the folded-BN inference chain - and stays differentiable like any nn.Module when autograd is
-        # recording (frozen-BatchNorm fine-tuning; the reference back-propagates through `dnn` in eval mode,
-        # receptive_field_analyzer.py:67,87): the backward then re-runs the layers with frozen statistics (train_graph).
-        if self.training:
-            from model import train_graph  # training graph (autograd.Function over the HIP kernels)
-            return train_graph.darknet_forward(self, x)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_graph
-            return train_graph.darknet_forward_eval_grad(self, x)
-        with torch.no_grad():
-            out = self.forward_nhwc(x)
-        # NCHW view of the NHWC head image: same values/shape as the reference's output; model.Inference's
-        # permute(0,2,3,1).contiguous() (model/__init__.py:122) is then free.
-        return out.permute(0, 3, 1, 2)
+    def _train_forward(self, x, frozen):
+        from model import train_graph  # training graph (autograd.Function over the HIP kernels)
+        return train_graph.darknet_forward_eval_grad(self, x) if frozen else train_graph.darknet_forward(self, x)
 
 
 class _PadPool(nn.Module):
@@ -418,10 +338,7 @@ class Tiny(Darknet):
         mods.append(Conv2d(config_channels.channels, model.output_channels(len(anchors), num_cls), 1, bn=False, act=False))
         self.layers = nn.Sequential(*mods)
         self.init()
-        self._cache = None
-        self._plans = _hip.PlanCache()
-        self.grad_ready_hook = None
-        self.profile = None
+        self._init_runtime()
 
     def init(self):
         _init_reference(self, nn.init.xavier_normal_)
@@ -433,13 +350,8 @@ class Tiny(Darknet):
         return [m.conv.weight for m in reversed([m for m in self.layers if isinstance(m, Conv2d)])]
 
     def forward_nhwc(self, x):
-        _hip.require_gpu(x)
+        x, B, cin0, H, W, dev = parts.enter(x)
         L = _hip.lib()
-        x = _hip.f32c(x)
-        B, cin0, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError('input size must be a multiple of 32 (got %dx%d)' % (H, W))
-        dev = x.device
         prep = self._prepare_eval(dev)
         st = _hip.stream()
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -478,13 +390,4 @@ class Tiny(Darknet):
             i += 1
         return cur
 
-    def forward(self, x):
-        if self.training:
-            from model import train_oplist
-            return train_oplist.forward(self, x)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from model import train_oplist
-            return train_oplist.forward(self, x, frozen=True)      # differentiable eval mode: the op-list graph with frozen statistics
-        with torch.no_grad():
-            out = self.forward_nhwc(x)
-        return out.permute(0, 3, 1, 2)
+    _train_forward = parts.InferMixin._train_forward      # the op-list graph, not Darknet's
