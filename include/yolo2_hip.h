@@ -383,6 +383,66 @@ int y2_warp_affine_images(const uint8_t* src, const int64_t* src_offset, const i
 int y2_collate_jitter_images(const uint8_t* src, const int64_t* offset, const int32_t* geom, const int32_t* jitter, const uint8_t* hsv_tab,
                              const float* lut, int32_t B, int32_t H, int32_t W, int32_t flags, float* out, y2_stream_t stream);
 
+/* Baseline JPEG decoding of the data pipeline (utils/data.py:77: cv2.imread, whose decoder is libjpeg-turbo) for a ragged batch on the device: the
+ * stage in front of y2_warp_affine_images / y2_collate_images / y2_collate_jitter_images (csrc/jpeg.hip; the decoder is csrc/jpeg.h, shared with the
+ * host function).  A worker parses the headers of a file with y2_jpeg_probe_host and ships the file's bytes and the descriptor record.
+ * Supported: baseline sequential DCT (SOF0), 8-bit, Huffman; ONE scan holding every component; three components Y Cb Cr with chroma sampled 1 x 1 and
+ * luma 1 x 1, 2 x 1 or 2 x 2, or one component (written to all three channels); restart intervals; up to four 8-bit quantisation tables, two DC and
+ * two AC Huffman tables; sides of 1 .. Y2_JPEG_MAX_DIM.  Everything else - progressive, extended, arithmetic, lossless, 12-bit, 16-bit quantisation
+ * tables, Huffman table ids 2 / 3, more than one scan, other sampling, four components, RGB (an Adobe APP14 marker with transform 0 on three
+ * components, or components named 'R' 'G' 'B' without a JFIF marker), DNL, an Exif orientation (tag 0x0112 of IFD0) of 2 .. 8, which cv2.imread would
+ * apply - is Y2_ENOSUP from the probe: no error, the caller decodes that file on the host.
+ *
+ * The recipe - libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling), restated.  VERIFIED bit for bit against Pillow's libjpeg-turbo on the
+ * fixtures of tests/golden/jpeg (tools/make_golden_jpeg.py); agreement with cv2.imread itself is unverified (OpenCV was not available).
+ * (a) Entropy decoding.  Canonical Huffman codes from the DHT counts and symbols.  Bytes FF 00 are one data byte FF.  Per block: a DC symbol t, t extra
+ *     bits, diff = extend(bits, t), DC = prediction + diff per component (prediction 0 at the scan start and behind every restart marker); then AC
+ *     symbols rs at zigzag position k = 1 ..: r = rs >> 4, n = rs & 15; n > 0: k += r, coefficient k = extend(n bits, n), k += 1; n == 0, r == 15
+ *     (ZRL): k += 16; n == 0 otherwise (EOB): the block ends.  extend(v, n) = v < 2^(n-1) ? v - 2^n + 1 : v.  With a restart interval of R MCUs,
+ *     behind every R MCUs less than 8 unread bits are dropped and the next two bytes must be FF D0+m (m counts the markers modulo 8).
+ * (b) Dequantisation and IDCT.  coefficient x table entry in 32-bit integers; jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2, the constants
+ *     2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172, a column pass descaled by 11 then a row pass descaled by 18 (descale(x, n) =
+ *     (x + 2^(n-1)) >> n, arithmetic), + 128, clamped to 0 .. 255.  (libjpeg's all-zero-AC shortcuts give the same values and are not taken; its
+ *     range-limit table wraps beyond +-512 where this clamps: outside what a valid stream produces.)  The arithmetic wraps modulo 2^32 instead of
+ *     overflowing.
+ * (c) Chroma upsampling, on the component's downsampled size cw x ch = ceil(size * samp / max_samp), not the block-padded one.  cw <= 2: replication.
+ *     Otherwise 2 x 1: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2, the first and last output samples of a row
+ *     copies;  2 x 2: per output row s[i] = 3 near[i] + far[i] (far = the row above for the upper output row, below for the lower; beyond the first /
+ *     last real row: that row itself), out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4, first column
+ *     (4 s[0] + 8) >> 4, last column (4 s[cw-1] + 7) >> 4.
+ * (d) Colour: x = level - 128; R = clamp(Y + ((91881 x_cr + 32768) >> 16)), B = clamp(Y + ((116130 x_cb + 32768) >> 16)),
+ *     G = clamp(Y + ((-22554 x_cb - 46802 x_cr + 32768) >> 16)), arithmetic shifts; bytes are stored B, G, R (cv2.imread's order).
+ *
+ * y2_jpeg_probe_host(data, nbytes, desc): HOST function.  Parses the markers of one file and fills the descriptor record desc
+ * [Y2_JPEG_DESC_BYTES] (zeroed when the file is refused).  Its first eight int32 are {height, width, components, luma h sampling, luma v sampling,
+ * restart interval, byte offset of the entropy-coded segment in the file, its length up to the first marker that is no RSTn}; behind them the table
+ * selectors, the quantisation tables and the Huffman tables in decoding form (csrc/jpeg.h: JpDesc).  0, Y2_ENOSUP (above) or Y2_EINVAL: no SOI,
+ * a segment length past the end, table ids or sampling factors out of range, zero dimensions, Huffman counts that over-subscribe the code space, a
+ * scan that names an undefined table, scan parameters other than 0 / 63 / 0.  Never reads outside [data, data + nbytes).
+ * y2_jpeg_workspace_bytes(desc, B): HOST function; desc [B] records in host memory.  The scratch a batch needs: B times the largest image's
+ * coefficient blocks (int16, in decoding order) and block-padded component planes (uint8), 3 bytes per padded component sample (4.5 per pixel at 4:2:0); Y2_EINVAL for a
+ * record that is none.
+ * y2_jpeg_decode_images: src: the packed file bytes, src_bytes long; file b starts at src + src_offset[b].  desc [B] records (4-byte aligned).
+ * dst / dst_offset / dst_geom [B][8]: the tables y2_collate_images and y2_warp_affine_images read next; columns 0-2 {row_stride_bytes, h, w} are
+ * read here and must be the descriptor's size; bytes of a row beyond 3 * w are not written.  ws: ws_bytes of scratch, 16-byte aligned; image b owns
+ * [b * p, (b + 1) * p), p = (ws_bytes / B) rounded down to 16.  status [B] int32, written on the device: 0 decoded; 1 bits were needed beyond the end
+ * of the segment; 2 no restart marker where an interval ends; 3 no such Huffman code, or a run past coefficient 63; 4 whole bytes left behind the last
+ * MCU - in these four cases the image holds what decoding zero bits from that point on yields (deterministic, the same on device and host);
+ * 5 the record is none, disagrees with dst_geom, or the image's source, destination or scratch lies outside src_bytes / dst_bytes / p: nothing is
+ * written for that image.  The other images of the batch are not affected.
+ * SAFETY, for ANY bytes in src and ANY contents of desc, src_offset, dst_offset and dst_geom: the device reads only inside [src, src + src_bytes) and
+ * the tables, writes only inside [dst, dst + dst_bytes), [ws, ws + ws_bytes) and status, and takes a bounded number of steps.  Every geometry value
+ * is derived in one place from range-checked descriptor fields (jp_layout) and checked against the three extents before an image is touched; a
+ * table selector is range-checked; a Huffman symbol's run cannot move past coefficient 63; a symbol index is masked to the table; a block takes at
+ * most 64 symbols and the block count comes from the checked size; reads past the segment's end yield zero bits.
+ * Three launches (entropy decoding: one workgroup per image; IDCT; upsampling + colour + store with 12-byte stores where dst + dst_offset[b] and
+ * the row stride are multiples of 4).  B == 0: nothing is launched.  B > 65535: Y2_ENOSUP.  Never allocates, never synchronises. */
+#define Y2_JPEG_MAX_DIM 16384
+#define Y2_JPEG_DESC_BYTES 4096
+int y2_jpeg_decode_images(const uint8_t* src, int64_t src_bytes, const int64_t* src_offset, const uint8_t* desc,
+                          uint8_t* dst, int64_t dst_bytes, const int64_t* dst_offset, const int32_t* dst_geom,
+                          uint8_t* ws, int64_t ws_bytes, int32_t* status, int32_t B, y2_stream_t stream);
+
 /* batch_iou_matrix: [Bt,N1,2]x2, [Bt,N2,2]x2 -> out [Bt,N1,N2]; iou_matrix is Bt = 1.  min_union = eps32.
  * mode 0: IoU (utils/iou/torch.py:47-61, 139-153);  mode 1: intersection area only (:24-44, 116-136). */
 int y2_iou_matrix(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
@@ -433,6 +493,14 @@ int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src_offset, co
  * Y2_EINVAL, nothing is written. */
 int y2_collate_jitter_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const int32_t* jitter, const uint8_t* hsv_tab,
                                   const float* lut, int32_t B, int32_t H, int32_t W, int32_t flags, float* out);
+/* The JPEG functions that run on the host (see y2_jpeg_decode_images).  y2_jpeg_decode_images_host: the same arguments as host pointers, the same
+ * bytes and the same status 0 .. 4.  The tables are checked first: an image that the device would give status 5 is Y2_EINVAL here, nothing is
+ * written. */
+int y2_jpeg_probe_host(const uint8_t* data, int64_t nbytes, uint8_t* desc);
+long long y2_jpeg_workspace_bytes(const uint8_t* desc, int32_t B);
+int y2_jpeg_decode_images_host(const uint8_t* src, int64_t src_bytes, const int64_t* src_offset, const uint8_t* desc,
+                               uint8_t* dst, int64_t dst_bytes, const int64_t* dst_offset, const int32_t* dst_geom,
+                               uint8_t* ws, int64_t ws_bytes, int32_t* status, int32_t B);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic mode (opt-in, process-global; one process per GPU, one stream).  By default the split-K weight gradient, the

@@ -60,6 +60,8 @@ EVAL_MATCH_MAX_G = 1024      # Y2_EVAL_MATCH_MAX_G (include/yolo2_hip.h)
 COLLATE_MAX_W = 4096         # Y2_COLLATE_MAX_W
 WARP_MAX_DIM = 16384         # Y2_WARP_MAX_DIM
 JITTER_MAX_BLUR = 7          # Y2_JITTER_MAX_BLUR
+JPEG_MAX_DIM = 16384         # Y2_JPEG_MAX_DIM
+JPEG_DESC_BYTES = 4096       # Y2_JPEG_DESC_BYTES
 
 SIGNATURES = {
     'y2_abi_version': [],
@@ -140,6 +142,10 @@ SIGNATURES = {
     'y2_warp_affine_images_host': [c_void_p] * 7 + [c_int, c_int, c_int, c_int],
     'y2_collate_jitter_images': [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     'y2_collate_jitter_images_host': [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p],
+    'y2_jpeg_probe_host': [c_void_p, ctypes.c_int64, c_void_p],
+    'y2_jpeg_workspace_bytes': [c_void_p, c_int],
+    'y2_jpeg_decode_images': [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p],
+    'y2_jpeg_decode_images_host': [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int],
     'y2_set_deterministic': [c_int, c_void_p, ctypes.c_longlong],
     'y2_get_deterministic': [],
     'y2_colstats_det': [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
@@ -187,6 +193,7 @@ def lib():
         l.y2_wino6_tiles.restype = ctypes.c_longlong
         l.y2_dwconv_wgrad_workspace_bytes.restype = ctypes.c_longlong
         l.y2_wino_wgrad_workspace_bytes_ex.restype = ctypes.c_longlong
+        l.y2_jpeg_workspace_bytes.restype = ctypes.c_longlong
         l.y2_build_info.argtypes = []
         l.y2_build_info.restype = ctypes.c_char_p
         _lib = l
@@ -434,7 +441,7 @@ def kernel_hash():
     """sha256 (16 hex digits) of the kernel sources the library is built from; None when the sources are not there."""
     import glob
     import hashlib
-    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
+    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(_HERE, 'csrc', 'jpeg.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
     if len(files) < 3 or not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha256()

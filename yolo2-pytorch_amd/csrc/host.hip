@@ -1,5 +1,6 @@
 // host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
-// y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host, y2_collate_jitter_images_host).
+// y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host, y2_collate_jitter_images_host, y2_jpeg_probe_host,
+// y2_jpeg_workspace_bytes, y2_jpeg_decode_images_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -15,6 +16,7 @@
 
 #include "yolo2_hip.h"
 #include "resample.h"
+#include "jpeg.h"
 
 namespace {
 
@@ -325,6 +327,55 @@ extern "C" int y2_collate_jitter_images_host(const uint8_t* src, const int64_t* 
                 }
                 for (int c = 0; c < 3; ++c) o[c * plane + (size_t)y * W + x] = tab[c * 256 + p[c]];
             }
+    }
+    return Y2_OK;
+}
+
+// ---- baseline JPEG (csrc/jpeg.h is the decoder; jpeg.hip runs the same functions on the device)
+
+static_assert(Y2_JPEG_DESC_BYTES == JP_DESC_BYTES && Y2_JPEG_MAX_DIM == JP_MAX_DIM, "include/yolo2_hip.h and csrc/jpeg.h disagree");
+
+extern "C" int y2_jpeg_probe_host(const uint8_t* data, int64_t nbytes, uint8_t* desc) {
+    if (!desc) return Y2_EINVAL;
+    JpDesc d;
+    const int rc = jp_probe(data, nbytes, &d);
+    if (rc != 0) memset(&d, 0, sizeof(d));          // a refused file leaves no half-filled record behind
+    memcpy(desc, &d, sizeof(d));
+    return rc;
+}
+
+extern "C" long long y2_jpeg_workspace_bytes(const uint8_t* desc, int32_t B) {
+    if (B < 0 || (B > 0 && !desc)) return Y2_EINVAL;
+    long long most = 0;
+    for (int b = 0; b < B; ++b) {
+        JpDesc d;
+        memcpy(&d, desc + (size_t)b * JP_DESC_BYTES, sizeof(d));
+        const JpLayout L = jp_layout(&d);
+        if (!L.ok) return Y2_EINVAL;
+        most = std::max(most, L.bytes);
+    }
+    return B * ((most + 15) & ~15LL);
+}
+
+// y2_jpeg_decode_images on host memory (jpeg.hip's three kernels, image by image).  The tables are readable here, so they are checked before anything
+// is written.
+extern "C" int y2_jpeg_decode_images_host(const uint8_t* src, int64_t src_bytes, const int64_t* src_offset, const uint8_t* desc,
+                                          uint8_t* dst, int64_t dst_bytes, const int64_t* dst_offset, const int32_t* dst_geom,
+                                          uint8_t* ws, int64_t ws_bytes, int32_t* status, int32_t B) {
+    if (B < 0 || src_bytes < 0 || dst_bytes < 0 || ws_bytes < 0) return Y2_EINVAL;
+    if (B == 0) return Y2_OK;
+    if (B > 65535) return Y2_ENOSUP;
+    if (!src || !src_offset || !desc || !dst || !dst_offset || !dst_geom || !ws || !status) return Y2_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15u) || (reinterpret_cast<uintptr_t>(desc) & 3u)) return Y2_EALIGN;
+    const long long per_image = (ws_bytes / B) & ~15LL;
+    for (int b = 0; b < B; ++b) {
+        const JpLayout L = jp_layout(reinterpret_cast<const JpDesc*>(desc + (size_t)b * JP_DESC_BYTES));
+        if (!jp_extents_ok(L, src_bytes, src_offset[b], dst_bytes, dst_offset[b], dst_geom + 8 * (size_t)b, per_image)) return Y2_EINVAL;
+    }
+    for (int b = 0; b < B; ++b) {
+        const JpDesc* d = reinterpret_cast<const JpDesc*>(desc + (size_t)b * JP_DESC_BYTES);
+        const JpLayout L = jp_layout(d);
+        status[b] = jp_decode_image_host(d, L, src + src_offset[b] + L.scan_offset, ws + (size_t)b * per_image, dst + dst_offset[b], dst_geom[8 * (size_t)b]);
     }
     return Y2_OK;
 }

@@ -16,7 +16,16 @@ With `transform_image` (transform.image.get_transform: RandomBlur, the HSV chain
 transform and adds `jitter`, `hsv_tab` (when the sequence goes through HSV) and `lut_b`, and `to_device` launches y2_collate_jitter_images IN PLACE
 of y2_collate_images (behind the warp launch, when there is one).  Without it, or with a sequence that is only BGR2RGB, nothing changes.
 
-What ships to the device is the source pixels as cv2.imread returned them - a quarter to a third of the bytes of the finished fp32 tensor."""
+What ships to the device is the source pixels as cv2.imread returned them - a quarter to a third of the bytes of the finished fp32 tensor.
+
+`Dataset` (the reference's class, utils/data.py:53-90) reads a sample's file with `read_image`: a baseline JPEG that y2_jpeg_probe_host accepts stays
+COMPRESSED - a `JpegImage` holding the file's bytes and its descriptor, with the `.shape`, `.ndim` and `.dtype` the label transforms read - and anything
+else is decoded on the host as before.  `Collate` packs the pixels of host-decoded samples first, exactly as above, and gives every JpegImage sample
+`offset` / `geom` rows that point at space reserved BEHIND them, which only exists on the device; the files' bytes travel as `jpeg`, `jpeg_offset`,
+`jpeg_desc`.  `to_device` allocates the whole pixel buffer, copies the host part and the files (about a tenth of the pixel bytes), launches
+y2_jpeg_decode_images in front of the launches above and adds `jpeg_status` without looking at it.  A batch without a JpegImage is untouched by all
+this: the same keys, the same bytes, the same launches."""
+import copy
 import os
 import pickle
 import random
@@ -38,6 +47,121 @@ def padding_labels(data, dim, labels=LABELS):
         padded[:len(label)] = label
         data[key] = padded
     return data
+
+
+def load_pickles(paths):
+    """The samples of the cache files (the reference's helper of this name)."""
+    data = []
+    for path in paths:
+        with open(path, 'rb') as f:
+            data += pickle.load(f)
+    return data
+
+
+class JpegImage(object):
+    """A baseline JPEG file the device will decode (y2_jpeg_decode_images): `data`, the file's bytes (uint8 [n]), and `desc`, the record
+    y2_jpeg_probe_host filled (uint8 [Y2_JPEG_DESC_BYTES]).  Stands where the decoded array would stand in `data['image']`: shape, ndim and dtype are
+    all the label transforms read of it."""
+    ndim = 3
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, data, desc):
+        self.data, self.desc = data, desc
+
+    @property
+    def shape(self):
+        height, width = self.desc[:8].view(np.int32)
+        return (int(height), int(width), 3)
+
+    def decode(self):
+        """The pixels, BGR uint8 [h, w, 3], by the host function (bit-identical to the device); raises when the stream is damaged."""
+        h, w, _ = self.shape
+        lib = _hip.lib()
+        ws = torch.empty(max(int(lib.y2_jpeg_workspace_bytes(self.desc.ctypes.data, 1)), 16), dtype=torch.uint8)
+        out, status = np.empty((h, w, 3), np.uint8), np.zeros(1, np.int32)
+        zero, geom = np.zeros(1, np.int64), np.array([[3 * w, h, w, 0, 0, h, w, 0]], np.int32)
+        _hip.check(lib.y2_jpeg_decode_images_host(self.data.ctypes.data, self.data.size, zero.ctypes.data, self.desc.ctypes.data, out.ctypes.data, out.size,
+                                                  zero.ctypes.data, geom.ctypes.data, ws.data_ptr(), ws.numel(), status.ctypes.data, 1), 'y2_jpeg_decode_images_host')
+        if status[0]:
+            raise ValueError('JpegImage.decode: damaged stream (status %d)' % status[0])
+        return out
+
+
+def probe_jpeg(data):
+    """The JpegImage of a file's bytes (uint8 [n]) when the device decoder supports it, else None (not a JPEG, damaged headers, or a kind of JPEG
+    include/yolo2_hip.h lists as not supported)."""
+    data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+    desc = np.zeros(_hip.JPEG_DESC_BYTES, np.uint8)
+    if data.size == 0 or _hip.lib().y2_jpeg_probe_host(data.ctypes.data, data.size, desc.ctypes.data) != 0:
+        return None
+    return JpegImage(data, desc)
+
+
+def _orient(image, orientation):
+    """An array turned as its Exif orientation says (what cv2.imread does on its own; Pillow does not)."""
+    if orientation in (2, 4, 5, 7):
+        image = image[:, ::-1]
+    if orientation in (3, 4):
+        image = image[::-1, ::-1]
+    elif orientation in (6, 7):
+        image = np.rot90(image, -1)
+    elif orientation in (5, 8):
+        image = np.rot90(image, 1)
+    return np.ascontiguousarray(image)
+
+
+def imread_host(path):
+    """cv2.imread(path) - BGR uint8 [h, w, 3] - or, where cv2 does not import, the same from Pillow: RGB -> BGR, the Exif orientation applied."""
+    try:
+        import cv2
+    except ImportError:
+        from PIL import Image
+        with Image.open(path) as image:
+            orientation = image.getexif().get(0x0112, 1)
+            return _orient(np.asarray(image.convert('RGB'))[..., ::-1], orientation)
+    return cv2.imread(path)
+
+
+def read_image(path, device_decode=True):
+    """What `data['image']` becomes: a JpegImage when y2_jpeg_probe_host accepts the file (the device decodes it), else the decoded array.
+    device_decode=False: always the array."""
+    if device_decode:
+        image = probe_jpeg(np.fromfile(path, np.uint8))
+        if image is not None:
+            return image
+    return imread_host(path)
+
+
+class Dataset(torch.utils.data.Dataset):
+    """The reference's class of this name (utils/data.py:53-90): a deep copy of sample `index`, its image read (`read_image` in place of cv2.imread),
+    `data['size']`, the transform on the labels, `cls` one-hot when `one_hot` (the number of classes) is given; the sample that raised is pickled
+    into `dir` before the exception goes on.  device_decode: leave supported JPEG files compressed for the device."""
+
+    def __init__(self, data, transform=lambda data: data, one_hot=None, shuffle=False, dir=None, device_decode=True):
+        self.data = data
+        if shuffle:
+            random.shuffle(self.data)
+        self.transform, self.one_hot, self.dir, self.device_decode = transform, one_hot, dir, device_decode
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, index):
+        data = copy.deepcopy(self.data[index])
+        try:
+            image = read_image(data['path'], self.device_decode)
+            data['image'] = image
+            data['size'] = np.array(image.shape[:2])
+            data = self.transform(data)
+            if self.one_hot is not None:
+                data['cls'] = np.eye(self.one_hot, dtype=np.float32)[np.asarray(data['cls'], np.int64)]          # (OneHotEncoder(one_hot, dtype=np.float32), dense)
+        except Exception:
+            if self.dir is not None:
+                os.makedirs(self.dir, exist_ok=True)
+                with open(os.path.join(self.dir, '%s.%s.pkl' % (type(self).__module__, type(self).__name__)), 'wb') as f:
+                    pickle.dump(data, f)
+            raise
+        return data
 
 
 def check_geometry(offset, geom, nbytes):
@@ -157,15 +281,36 @@ class Collate(object):
         offset = np.zeros(len(samples), np.int64)
         geom = np.zeros((len(samples), 8), np.int32)
         pos = 0
+        compressed = [b for b, data in enumerate(samples) if isinstance(data['image'], JpegImage)]
         for b, data in enumerate(samples):
-            h, w = data['image'].shape[:2]
-            offset[b] = pos
-            geom[b] = (3 * w, h, w) + tuple(data['window']) + (int(bool(data['flip'])),)
-            pos += 3 * h * w
+            if b not in compressed:
+                h, w = data['image'].shape[:2]
+                offset[b] = pos
+                geom[b] = (3 * w, h, w) + tuple(data['window']) + (int(bool(data['flip'])),)
+                pos += 3 * h * w
         raw = np.empty(pos, np.uint8)
         for b, data in enumerate(samples):
-            raw[offset[b]:offset[b] + data['image'].size] = data['image'].reshape(-1)
+            if b not in compressed:
+                raw[offset[b]:offset[b] + data['image'].size] = data['image'].reshape(-1)
         extra = {}
+        if compressed:
+            # the decoded images live behind the host's pixels, on the device only: rows and images start where the decoder's 12-byte stores are aligned
+            for b in compressed:
+                h, w = samples[b]['image'].shape[:2]
+                stride = -(-3 * w // ROT_ROW_ALIGN) * ROT_ROW_ALIGN
+                pos = -(-pos // ROT_IMAGE_ALIGN) * ROT_IMAGE_ALIGN
+                offset[b] = pos
+                geom[b] = (stride, h, w) + tuple(samples[b]['window']) + (int(bool(samples[b]['flip'])),)
+                pos += h * stride
+            files = [samples[b]['image'] for b in compressed]
+            jpeg_offset = np.cumsum([0] + [f.data.size for f in files]).astype(np.int64)
+            desc = np.stack([f.desc for f in files])
+            need = int(_hip.lib().y2_jpeg_workspace_bytes(desc.ctypes.data, len(files)))
+            if need < 0:
+                raise ValueError('collate: a JpegImage carries a descriptor that y2_jpeg_probe_host did not fill')
+            extra.update(jpeg=torch.from_numpy(np.concatenate([f.data for f in files])), jpeg_offset=torch.from_numpy(jpeg_offset[:-1].copy()),
+                         jpeg_desc=torch.from_numpy(desc), jpeg_index=torch.from_numpy(np.array(compressed, np.int64)),
+                         jpeg_dst=torch.from_numpy(offset[compressed]), jpeg_geom=torch.from_numpy(geom[compressed]), jpeg_ws_bytes=need, raw_bytes=pos)
         if any('rotate' in data for data in samples):
             # every sample goes through the warp stage (an un-rotated one with the identity, an exact copy): what was packed above is its source, and
             # offset / geom move on to the rotated images inside the intermediate buffer
@@ -181,9 +326,9 @@ class Collate(object):
                 offset[b] = pos
                 geom[b, :3] = (stride, h, w)
                 pos += -(-h * stride // ROT_IMAGE_ALIGN) * ROT_IMAGE_ALIGN
-            check_warp(src_offset, src_geom, warp, raw.size, offset, geom, pos)
-            extra = dict(src_offset=torch.from_numpy(src_offset), src_geom=torch.from_numpy(src_geom), warp=torch.from_numpy(warp), rot_bytes=pos,
-                       rot_size=(int(geom[:, 1].max()), int(geom[:, 2].max())))
+            check_warp(src_offset, src_geom, warp, extra.get('raw_bytes', raw.size), offset, geom, pos)
+            extra.update(src_offset=torch.from_numpy(src_offset), src_geom=torch.from_numpy(src_geom), warp=torch.from_numpy(warp), rot_bytes=pos,
+                         rot_size=(int(geom[:, 1].max()), int(geom[:, 2].max())))
         if self.transform_image is not None and self.transform_image.active:
             records = [data['jitter'] for data in samples]
             jitter = np.array([tuple(r['blur']) + (int(r['hsv']), 0) for r in records], np.int32).reshape(-1, 4)
@@ -233,7 +378,12 @@ def to_device(batch, device=None, out=None, rot=None):
     torch.empty - and y2_collate_images reads that buffer instead of `raw`.  The result carries it as `rot`.  `batch['fill']` (0xC2C1C0, one byte per
     source channel; default 0, what the reference passes) is the level outside the source.  Without `warp`, `rot` is not touched.
     A batch with `jitter` (Collate had a transform_image) launches y2_collate_jitter_images instead of y2_collate_images: `jitter` int32 [B, 4],
-    `hsv_tab` uint8 [B, 3, 256] (optional) and `lut_b` fp32 [B, 3, 256], the per-image table that takes the place of `lut`."""
+    `hsv_tab` uint8 [B, 3, 256] (optional) and `lut_b` fp32 [B, 3, 256], the per-image table that takes the place of `lut`.
+    A batch with `jpeg` (a sample's image is a JpegImage) takes y2_jpeg_decode_images (three kernels; 'cpu': y2_jpeg_decode_images_host) in front of all
+    that: the pixel buffer of `batch['raw_bytes']` bytes is allocated on `device`, the host-decoded pixels of `raw` are copied to its front, the files
+    (`jpeg`, `jpeg_offset`, `jpeg_desc`) follow, and the decoder writes the JpegImage samples where `jpeg_dst` / `jpeg_geom` (their `offset` / `geom`
+    rows before any rotation) say.  The result carries the buffer as `raw` and `jpeg_status` (int32, one per `jpeg_index` entry, 0 = decoded: the
+    status column of include/yolo2_hip.h) on `device`, un-synchronised: the caller decides when to look at it."""
     raw = batch['raw']
     if device is None:
         device = raw.device if raw.is_cuda else torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
@@ -242,15 +392,33 @@ def to_device(batch, device=None, out=None, rot=None):
         device = torch.device('cuda', torch.cuda.current_device())
     H, W = (int(v) for v in batch['size'])
     warped = 'warp' in batch
-    pixels = int(batch['rot_bytes']) if warped else raw.numel()          # the buffer that offset / geom index
+    compressed = 'jpeg' in batch
+    source = int(batch['raw_bytes']) if compressed else raw.numel()      # the buffer of source pixels: `raw`, and behind it the images the device decodes
+    pixels = int(batch['rot_bytes']) if warped else source               # the buffer that offset / geom index
     if not batch['geom'].is_cuda and not batch['offset'].is_cuda:
         check_geometry(batch['offset'].numpy(), batch['geom'].numpy(), pixels)
         if warped and not any(batch[k].is_cuda for k in ('src_offset', 'src_geom', 'warp')):
-            check_warp(batch['src_offset'].numpy(), batch['src_geom'].numpy(), batch['warp'].numpy(), raw.numel(), batch['offset'].numpy(), batch['geom'].numpy(), pixels)
+            check_warp(batch['src_offset'].numpy(), batch['src_geom'].numpy(), batch['warp'].numpy(), source, batch['offset'].numpy(), batch['geom'].numpy(), pixels)
     jittered = 'jitter' in batch
     if jittered and not any(batch[k].is_cuda for k in ('jitter', 'hsv_tab', 'lut_b') if k in batch):
         check_jitter(batch['jitter'].numpy(), batch.get('hsv_tab'), batch['lut_b'], batch['geom'].size(0))
-    res = {k: (v.to(device, non_blocking=v.is_pinned()) if torch.is_tensor(v) else v) for k, v in batch.items()}
+    res = {k: (v.to(device, non_blocking=v.is_pinned()) if torch.is_tensor(v) and not (compressed and k == 'raw') else v) for k, v in batch.items()}
+    jpeg_args = None
+    if compressed:
+        if raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() > source:
+            raise ValueError('to_device: raw must be uint8 [n] with n <= raw_bytes')
+        res['raw'] = torch.empty(source, dtype=torch.uint8, device=device)
+        if raw.numel():
+            res['raw'][:raw.numel()].copy_(raw, non_blocking=raw.is_pinned())
+        files, at, desc, dst_at, dst_geom = (res[k].contiguous() for k in ('jpeg', 'jpeg_offset', 'jpeg_desc', 'jpeg_dst', 'jpeg_geom'))
+        n = desc.size(0)
+        if (files.dtype != torch.uint8 or desc.dtype != torch.uint8 or desc.dim() != 2 or desc.size(1) != _hip.JPEG_DESC_BYTES or at.dtype != torch.int64
+                or dst_at.dtype != torch.int64 or dst_geom.dtype != torch.int32 or at.numel() != n or dst_at.numel() != n or tuple(dst_geom.shape) != (n, 8)):
+            raise ValueError('to_device: jpeg must be uint8, jpeg_desc uint8 [n, %d], jpeg_offset and jpeg_dst int64 [n], jpeg_geom int32 [n, 8]' % _hip.JPEG_DESC_BYTES)
+        ws = torch.empty(max(int(batch['jpeg_ws_bytes']), 16), dtype=torch.uint8, device=device)
+        res['jpeg_status'] = torch.empty(n, dtype=torch.int32, device=device)
+        jpeg_args = (files.data_ptr(), files.numel(), at.data_ptr(), desc.data_ptr(), res['raw'].data_ptr(), source, dst_at.data_ptr(), dst_geom.data_ptr(),
+                     ws.data_ptr(), ws.numel(), res['jpeg_status'].data_ptr(), n)
     raw, offset, geom = res['raw'], res['offset'], res['geom']
     B = geom.size(0)
     if raw.dtype != torch.uint8 or offset.dtype != torch.int64 or geom.dtype != torch.int32 or geom.dim() != 2 or geom.size(1) != 8 or offset.numel() != B:
@@ -294,10 +462,14 @@ def to_device(batch, device=None, out=None, rot=None):
     name = 'y2_collate_jitter_images' if jittered else 'y2_collate_images'
     if device.type == 'cuda':
         with torch.cuda.device(device):
+            if compressed:
+                _hip.check(_hip.lib().y2_jpeg_decode_images(*jpeg_args, _hip.stream()), 'y2_jpeg_decode_images')
             if warped:
                 _hip.check(_hip.lib().y2_warp_affine_images(*warp_args, _hip.stream()), 'y2_warp_affine_images')
             _hip.check(getattr(_hip.lib(), name)(*args, _hip.stream()), name)
     else:
+        if compressed:
+            _hip.check(_hip.lib().y2_jpeg_decode_images_host(*jpeg_args), 'y2_jpeg_decode_images_host')
         if warped:
             _hip.check(_hip.lib().y2_warp_affine_images_host(*warp_args), 'y2_warp_affine_images_host')
         _hip.check(getattr(_hip.lib(), name + '_host')(*args), name + '_host')
