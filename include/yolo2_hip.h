@@ -443,6 +443,41 @@ int y2_jpeg_decode_images(const uint8_t* src, int64_t src_bytes, const int64_t* 
                           uint8_t* dst, int64_t dst_bytes, const int64_t* dst_offset, const int32_t* dst_geom,
                           uint8_t* ws, int64_t ws_bytes, int32_t* status, int32_t B, y2_stream_t stream);
 
+/* Choosing a dataset's anchors (dimension_cluster.py): k-means on the distance 1 - IoU over box sizes, R restarts ("trials") in one launch, one
+ * workgroup per trial (csrc/kmeans.hip; the arithmetic is csrc/kmeans.h, shared with the host functions).  The reference runs
+ * nltk.cluster.kmeans.KMeansClusterer with distance(a, b) = 1 - utils.iou.numpy.iou(-a, a, -b, b) on float64 data.  nltk was not available: the
+ * algorithm below is KMeansClusterer RESTATED FROM MEMORY, agreement with a real nltk run is UNVERIFIED, and this text is the contract.
+ * All arithmetic is fp64, one rounding per operation (-ffp-contract=off).  size [N][2]: (height, width) per box, like yx - the half-extents a of a box
+ * centred on the origin.
+ * (a) IoU, in the operation order of utils/iou/numpy.py:iou with its default `min`: ih = 2 min(a.h, b.h), iw = 2 min(a.w, b.w) (the difference
+ *     min(a, b) - max(-a, -b) is exactly that); inter = ih iw; area1 = (2 a.h)(2 a.w), area2 likewise; union = max((area1 + area2) - inter,
+ *     DBL_EPSILON); iou = inter / union; dist = 1 - iou.  min and max are numpy's: a NaN operand is the result.
+ * (b) Classification (classify_vectorspace): best = dist(x, mean[0]) unconditionally; mean k = 1 .. K-1 replaces it only when dist < best (strict):
+ *     ties and NaN stay with the lower index.
+ * (c) Centroid.  nltk adds a cluster's members one after the other, which no parallel reduction reproduces, so the order is fixed HERE, independently
+ *     of how a kernel is launched: per cluster and component 256 lane partials, each starting at +0.0 and adding the members i = l (mod 256) in
+ *     increasing i; then the tree for s = 128, 64 .. 1: p[l] += p[l + s] for l < s; centroid = p[0] / (double)count.  (Adding +0.0 for a non-member
+ *     is bit-identical to skipping it.)
+ * (d) One iteration (_cluster_vectorspace): classify all N boxes; if a cluster is empty the trial ends with status 1 (the reference aborts on an
+ *     assertion there) and the means stay those the iteration started from; otherwise the new means, difference = sum_k dist(old_k, new_k) added in
+ *     increasing k from 0.0, the means become the new means, and the trial has converged when difference < conv_test (the reference: 1e-6).
+ * (e) max_iter iterations without convergence: status 2 (nltk has no limit).  K >= N: no iteration runs (nltk's num_means < len(vectors) guard), the
+ *     initial means are the result, iters 0, status 0.
+ * (f) Initial means of trial r: size[init[r][k]].  An index outside [0, N) is never dereferenced: the trial ends with status 3 and zeroed outputs.
+ * (g) Final pass: one more classification against the final means gives counts [K] and cost = sum of dist in the lane / tree order of (c); the mean
+ *     IoU of the anchors is 1 - cost / N.
+ * iters[r]: the iterations that replaced the means (the one that found an empty cluster is not counted).
+ * Y2_EINVAL: N, K, R or max_iter <= 0, a null pointer.  Y2_ENOSUP: K > Y2_KMEANS_MAX_K (the paper explores up to 15; YOLOv2 uses 5, its successors
+ * 9), R > 65535.  Y2_EALIGN: size, means or cost not 8-byte aligned.  One launch; never allocates, never synchronises.
+ * SAFETY for ANY values in size and init: a box index is a loop counter, an initial index is range-checked, a winner is an integer in [0, K).  The
+ * Python layer rejects NaN, zero and negative sizes and out-of-range indices before they reach the library.
+ * y2_anchor_assign: classification (b) of N boxes against arbitrary means [K][2] (device memory): index [N] int32 and / or iou [N] double (the IoU
+ * with the winning mean), either may be NULL.  A grid-stride kernel. */
+#define Y2_KMEANS_MAX_K 16
+int y2_anchor_kmeans(const double* size, int32_t N, int32_t K, const int32_t* init, int32_t R, int32_t max_iter, double conv_test,
+                     double* means, int32_t* iters, int32_t* status, double* cost, int32_t* counts, y2_stream_t stream);
+int y2_anchor_assign(const double* size, int32_t N, const double* means, int32_t K, int32_t* index, double* iou, y2_stream_t stream);
+
 /* batch_iou_matrix: [Bt,N1,2]x2, [Bt,N2,2]x2 -> out [Bt,N1,N2]; iou_matrix is Bt = 1.  min_union = eps32.
  * mode 0: IoU (utils/iou/torch.py:47-61, 139-153);  mode 1: intersection area only (:24-44, 116-136). */
 int y2_iou_matrix(const float* yx_min1, const float* yx_max1, const float* yx_min2, const float* yx_max2,
@@ -501,6 +536,11 @@ long long y2_jpeg_workspace_bytes(const uint8_t* desc, int32_t B);
 int y2_jpeg_decode_images_host(const uint8_t* src, int64_t src_bytes, const int64_t* src_offset, const uint8_t* desc,
                                uint8_t* dst, int64_t dst_bytes, const int64_t* dst_offset, const int32_t* dst_geom,
                                uint8_t* ws, int64_t ws_bytes, int32_t* status, int32_t B);
+/* y2_anchor_kmeans / y2_anchor_assign on host memory (dimension_cluster.cluster on CPU data): the same functions of csrc/kmeans.h, the trials one
+ * after the other on the calling thread; every output is bit-identical to the device entry point. */
+int y2_anchor_kmeans_host(const double* size, int32_t N, int32_t K, const int32_t* init, int32_t R, int32_t max_iter, double conv_test,
+                          double* means, int32_t* iters, int32_t* status, double* cost, int32_t* counts);
+int y2_anchor_assign_host(const double* size, int32_t N, const double* means, int32_t K, int32_t* index, double* iou);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic mode (opt-in, process-global; one process per GPU, one stream).  By default the split-K weight gradient, the

@@ -62,6 +62,7 @@ WARP_MAX_DIM = 16384         # Y2_WARP_MAX_DIM
 JITTER_MAX_BLUR = 7          # Y2_JITTER_MAX_BLUR
 JPEG_MAX_DIM = 16384         # Y2_JPEG_MAX_DIM
 JPEG_DESC_BYTES = 4096       # Y2_JPEG_DESC_BYTES
+KMEANS_MAX_K = 16             # Y2_KMEANS_MAX_K
 
 SIGNATURES = {
     'y2_abi_version': [],
@@ -146,6 +147,10 @@ SIGNATURES = {
     'y2_jpeg_workspace_bytes': [c_void_p, c_int],
     'y2_jpeg_decode_images': [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p],
     'y2_jpeg_decode_images_host': [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int],
+    'y2_anchor_kmeans': [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double] + [c_void_p] * 5 + [c_void_p],
+    'y2_anchor_kmeans_host': [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double] + [c_void_p] * 5,
+    'y2_anchor_assign': [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    'y2_anchor_assign_host': [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
     'y2_set_deterministic': [c_int, c_void_p, ctypes.c_longlong],
     'y2_get_deterministic': [],
     'y2_colstats_det': [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p],
@@ -441,7 +446,7 @@ def kernel_hash():
     """sha256 (16 hex digits) of the kernel sources the library is built from; None when the sources are not there."""
     import glob
     import hashlib
-    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(_HERE, 'csrc', 'jpeg.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
+    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(_HERE, 'csrc', 'jpeg.h'), os.path.join(_HERE, 'csrc', 'kmeans.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
     if len(files) < 3 or not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha256()

@@ -1,6 +1,6 @@
 // host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
 // y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host, y2_collate_jitter_images_host, y2_jpeg_probe_host,
-// y2_jpeg_workspace_bytes, y2_jpeg_decode_images_host).
+// y2_jpeg_workspace_bytes, y2_jpeg_decode_images_host, y2_anchor_kmeans_host, y2_anchor_assign_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -17,6 +17,7 @@
 #include "yolo2_hip.h"
 #include "resample.h"
 #include "jpeg.h"
+#include "kmeans.h"
 
 namespace {
 
@@ -377,5 +378,30 @@ extern "C" int y2_jpeg_decode_images_host(const uint8_t* src, int64_t src_bytes,
         const JpLayout L = jp_layout(d);
         status[b] = jp_decode_image_host(d, L, src + src_offset[b] + L.scan_offset, ws + (size_t)b * per_image, dst + dst_offset[b], dst_geom[8 * (size_t)b]);
     }
+    return Y2_OK;
+}
+
+// ---- anchors by k-means on 1 - IoU (csrc/kmeans.h is the arithmetic and the trial itself; kmeans.hip runs the same functions on the device)
+
+static_assert(Y2_KMEANS_MAX_K == KM_MAX_K, "include/yolo2_hip.h and csrc/kmeans.h disagree");
+
+extern "C" int y2_anchor_kmeans_host(const double* size, int32_t N, int32_t K, const int32_t* init, int32_t R, int32_t max_iter, double conv_test,
+                                     double* means, int32_t* iters, int32_t* status, double* cost, int32_t* counts) {
+    if (N <= 0 || K <= 0 || R <= 0 || max_iter <= 0) return Y2_EINVAL;
+    if (!size || !init || !means || !iters || !status || !cost || !counts) return Y2_EINVAL;
+    if (K > Y2_KMEANS_MAX_K || R > 65535) return Y2_ENOSUP;
+    if ((reinterpret_cast<uintptr_t>(size) | reinterpret_cast<uintptr_t>(means) | reinterpret_cast<uintptr_t>(cost)) & 7u) return Y2_EALIGN;
+    std::vector<double> part((size_t)(2 * K + 1) * KM_LANES);
+    for (int r = 0; r < R; ++r)
+        km_trial_host(size, N, K, init + (size_t)r * K, max_iter, conv_test, means + 2 * (size_t)r * K, iters + r, status + r, cost + r,
+                      counts + (size_t)r * K, part.data());
+    return Y2_OK;
+}
+
+extern "C" int y2_anchor_assign_host(const double* size, int32_t N, const double* means, int32_t K, int32_t* index, double* iou) {
+    if (N <= 0 || K <= 0 || !size || !means) return Y2_EINVAL;
+    if (K > Y2_KMEANS_MAX_K) return Y2_ENOSUP;
+    if ((reinterpret_cast<uintptr_t>(size) | reinterpret_cast<uintptr_t>(means) | reinterpret_cast<uintptr_t>(iou)) & 7u) return Y2_EALIGN;
+    km_assign_host(size, N, means, K, index, iou);
     return Y2_OK;
 }

@@ -80,4 +80,20 @@ def ensure_device(t, device_id=None, non_blocking=False):
     return t.cuda(device_id, non_blocking) if torch.cuda.is_available() else t
 
 
+def image_size(path):
+    """(width, height) of an image file, Pillow's order (utils/__init__.py:124-126).  A JPEG that utils.data.probe_jpeg accepts is answered from
+    its headers by the library; anything else needs Pillow."""
+    from . import data
+    image = data.probe_jpeg(np.fromfile(path, np.uint8))
+    if image is not None:
+        height, width, _ = image.shape
+        return width, height
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError('utils.image_size: %s is no baseline JPEG the library parses, and Pillow is not installed to read it' % path)
+    with Image.open(path) as image:
+        return image.size
+
+
 from . import optim  # noqa: E402,F401  (utils.optim.SGD / Adam / clip_grad_norm_ for the ini lambda, config.ini:72)
