@@ -361,9 +361,11 @@ def test_conv0_matches_fp64_reference(B, cin, cout, H, W):
 
 @pytest.mark.parametrize('B,H,W,cout', [(9, 416, 416, 32), (40, 208, 224, 32), (3, 330, 500, 16)])
 def test_conv0_persistent_workgroups_walk_several_tiles(B, H, W, cout):
-    """More 16 x 32-pixel tiles than the persistent grid has workgroups (2,048): a workgroup computes its 2nd, 3rd ... tile out of the patches it staged two tiles
-    ahead (three LDS buffers, csrc/conv0_fwd.hip).  Inference form (pooled output only), training form (raw z + statistics) and - ragged size, 16 channels -
-    the general kernel against the fp64 reference."""
+    """More 16 x 32-pixel tiles than the persistent grid has workgroups (2,048): the first two shapes have 3,042 and 3,640 tiles, so 994 and 1,592 of the 2,048 workgroups
+    compute a second tile, out of the patch staged in front of the loop (three LDS buffers, csrc/conv0_fwd.hip; no workgroup reaches a third tile, so the
+    in-loop staging never runs here).  Inference form (pooled output only) and training form (raw z + statistics) against the fp64 reference.  The third
+    shape - ragged size, 16 channels: the general kernel - has 1,008 tiles and does NOT walk: one tile per workgroup.  The walks of three and more tiles
+    and the general kernel's walks are in tests/test_gpu_conv0.py."""
     import _hip
     L = _hip.lib()
     d = dev()
