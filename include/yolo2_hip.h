@@ -230,6 +230,11 @@ int y2_conv_fwd_batch(const y2_conv_params* params, int count, y2_stream_t strea
 int y2_conv0_fwd(const float* x_nchw, const float* w, const float* scale, const float* shift,
                  float* y, float* y_pool, double* stats,
                  int B, int H, int W, int Cin, int Cout, int ldy, int ldp, float slope, y2_stream_t stream);
+/* The training forward of the first layer as a producer of z_sel (see y2_bn_act_fwd_sel): raw z (pixel stride ldz), its statistics, and z_sel
+ * [B,H/2,W/2,Cout] (pixel stride ldzs) = per window the first z_q in scan order that maximises sign(gamma[c]) * z_q (strict comparison; gamma = the
+ * BatchNorm weight, known before the batch statistics are).  z and stats are those of y2_conv0_fwd(x, w, NULL, NULL, z, NULL, stats, ..., 1.0). */
+int y2_conv0_fwd_sel(const float* x_nchw, const float* w, const float* gamma, float* z, float* z_sel, double* stats,
+                     int B, int H, int W, int Cin, int Cout, int ldz, int ldzs, y2_stream_t stream);
 
 /* nn.MaxPool2d(kernel_size=2) (model/yolo2.py:79,86,97) on NHWC; H, W even (16-B vector path when C, ldx, ldy are multiples of 4). */
 int y2_maxpool2_fwd(const float* x, float* y, int B, int H, int W, int C, int ldx, int ldy, y2_stream_t stream);
@@ -635,6 +640,21 @@ int y2_bn_act_bwd_ex(const float* z, const float* scale, const float* shift, con
                      float slope, const float* dy_full, int ldf, int foff, int fmode, const float* dy_pool, int ldp, int poff,
                      const float* dy_full2, int ld2, const float* residual, int ldr, float* dres, int lddr,
                      double* sums, float* dz, int ldd, int B, int H, int W, int C, int ldz, int has_bn, y2_stream_t stream);
+
+/* Pooled blocks without a full-resolution consumer (conv -> BatchNorm(batch statistics) -> LeakyReLU -> MaxPool2d(2), model/yolo2.py:78-96): the
+ * quarter-resolution companion z_sel [B,H/2,W/2,C] (pixel stride ldzs) holds, per window and channel, the pre-activation z of the element the pool
+ * selects: with s = sign(gamma[c]) the FIRST q in scan order that maximises s*z_q (strict comparison; s = 0: q = 0).  The activation is monotone in z,
+ * so LeakyReLU(z_sel*scale + shift) IS the pooled activation, bit for bit (y2_bn_act_fwd over z_sel as an un-pooled [B,H/2,W/2,C] map), and the pooled
+ * gradient is non-zero at that element only, so the backward's sums need no other z.
+ * y2_bn_act_fwd_sel: y2_bn_act_fwd's pooled form (y = NULL) that also writes z_sel = z at the window's first maximal ACTIVATION (exactly the element
+ * y2_bn_act_bwd routes the gradient to; it differs from the definition above only where two different z round to one activation).
+ * y2_bn_act_bwd_sel: y2_bn_act_bwd for dy_pool only and has_bn = 1 whose pass 1 (sums) reads (z_sel, dy_pool) - a quarter of z - while pass 2 (dz, NULL:
+ * sums only) reads the full z as before. */
+int y2_bn_act_fwd_sel(const float* z, const float* scale, const float* shift, float slope, float* y_pool, float* z_sel,
+                      int B, int H, int W, int C, int ldz, int ldp, int poff, int ldzs, y2_stream_t stream);
+int y2_bn_act_bwd_sel(const float* z, const float* z_sel, int ldzs, const float* scale, const float* shift, const float* mean, const float* invstd,
+                      const float* gamma, float slope, const float* dy_pool, int ldp, int poff, double* sums, float* dz, int ldd,
+                      int B, int H, int W, int C, int ldz, y2_stream_t stream);
 
 /* Tile count T of the 4x4-tile Winograd forms for a batch of B maps of H x W (per-image grid, or the batch mosaic where that is smaller: csrc/common.h,
  * Wino6Grid) - the row count of the transformed operands [36][T][C] of Y2_ALGO_WINOGRAD_F43(_PRE) / y2_wino_wgrad_ex (bits 1, 2). */

@@ -29,6 +29,7 @@ struct Conv0Args {
     int B, H, W, Cout, ldy, ldp;
     float slope;
     int tiles_y, tiles_x, ntiles;
+    const float* pool_sign;      // y2_conv0_fwd_sel (raw outputs only): the BatchNorm weight; the pooled output receives z_sel, not the window maximum
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -57,6 +58,9 @@ struct StepTap {
 // inside the image, Cout == 32 * NBLK and the outputs are dense (ld == Cout), so the epilogue has no bounds checks and every store is
 // base + lane + constant.  RAW: no affine and no activation (the training forward: z and its statistics).  With OUT and FULL the epilogue
 // is straight-line code (the runtime-flag form spends more instructions on tests than on arithmetic).  OUT = -1, FULL = false: the general kernel.
+// z_sel (OUT = 7 with RAW, or the general kernel with a.pool_sign): the pooled output is the window's FIRST z_q in scan order that maximises
+// sign(pool_sign[n]) * z_q under a strict comparison - one of the four stored values, the pre-activation nn.MaxPool2d selects behind a BatchNorm whose
+// weight has that sign and a LeakyReLU (include/yolo2_hip.h: y2_conv0_fwd_sel).
 //
 // What bounds this kernel (round 6, `tools/conv0_probe.py` with the -DY2_C0_DBG builds): a tile's 56 MFMAs per wave alone run at 0.75 of the matrix rate; the
 // patch staging and the epilogue each ADDED their whole duration on top (0.167 + 0.053 + 0.054 ms at batch 64) - with 3 resident waves per SIMD a wave's
@@ -71,6 +75,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const Conv0Args a) {
     // (negation commutes with every rounding, so the accumulators are the reference's times +-1), and with |scale| >= 0 and 0 <= slope <= 1 (launch0 checks)
     // z -> leaky(z * |scale| + shift) is non-decreasing in every rounding step, so it commutes with max.
     constexpr bool POOL_FIRST = FULL && OUT == 2 && !RAW;
+    const bool sel = (OUT == 7 && RAW) ? true : (OUT < 0 ? a.pool_sign != nullptr : false);
     constexpr int K = CIN * 9;
     constexpr int KS = (K + 1) / 2;
     constexpr int PR = TH + 2;                          // patch rows per channel
@@ -88,6 +93,13 @@ __global__ __launch_bounds__(256) void conv0_kernel(const Conv0Args a) {
         const int n = j * 32 + l31;
         sc[j] = (!RAW && a.scale != nullptr && n < a.Cout) ? a.scale[n] : 1.f;
         sh[j] = (!RAW && a.shift != nullptr && n < a.Cout) ? a.shift[n] : 0.f;
+    }
+    float sg[NBLK];          // sel: sign of the channel's BatchNorm weight (+1, 0, -1)
+#pragma unroll
+    for (int j = 0; j < NBLK; ++j) {
+        const int n = j * 32 + l31;
+        const float gm = (sel && n < a.Cout) ? a.pool_sign[n] : 0.f;
+        sg[j] = gm > 0.f ? 1.f : (gm < 0.f ? -1.f : 0.f);
     }
     // ---- weights: B[k][n] = w[n][k'], lane holds n = l31 (+32 per block) and the MFMA's k = 2s + half.  The MFMA k index is a PERMUTATION of the taps
     // k' = (c, ky, kx) (state_dict order) chosen so that the two taps of a step lie a constant LDS distance apart within a group of steps (StepTap below): a lane's
@@ -279,7 +291,18 @@ __global__ __launch_bounds__(256) void conv0_kernel(const Conv0Args a) {
                     }
                 }
                 if (has_pool && (FULL || (Y < a.H && X < a.W))) {
-                    const float pm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                    float pm;
+                    if (sel) {
+                        float best = sg[j] * v[0];
+                        pm = v[0];
+#pragma unroll
+                        for (int q = 1; q < 4; ++q) {
+                            const float key = sg[j] * v[q];
+                            if (key > best) { best = key; pm = v[q]; }
+                        }
+                    } else {
+                        pm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+                    }
                     (pb + (2 * g * ldp + j * 32))[plane] = pm;
                 }
             }
@@ -320,6 +343,11 @@ int launch0(const Conv0Args& a, hipStream_t s) {
         const int out = (a.y != nullptr ? 1 : 0) | (a.y_pool != nullptr ? 2 : 0) | (a.stats != nullptr ? 4 : 0);
         const bool raw = a.scale == nullptr && a.shift == nullptr && a.slope == 1.f;           // the training forward: z and its statistics
         const bool mono = a.slope >= 0.f && a.slope <= 1.f;                                      // the pool-first epilogue's condition
+        if (a.pool_sign != nullptr && a.Cout == 32 && out == 7 && raw) {          // y2_conv0_fwd_sel: z, statistics and z_sel
+            Y2_LAUNCH("conv0_kernel", flops, (conv0_kernel<3, 1, 7, true, true>), dim3((unsigned)grid), dim3(256), 0, s, a);
+            Y2_LAUNCH_CHECK();
+            return Y2_OK;
+        }
 #define Y2_C0(NB_, OUT_, RAW_) Y2_LAUNCH("conv0_kernel", flops, (conv0_kernel<3, NB_, OUT_, true, RAW_>), dim3((unsigned)grid), dim3(256), 0, s, a)
         bool done = true;
         if (a.Cout == 32) {
@@ -339,9 +367,25 @@ int launch0(const Conv0Args& a, hipStream_t s) {
 
 }  // namespace
 
+// pool_sign: y2_conv0_fwd_sel's BatchNorm weight (NULL: y2_conv0_fwd).  The shared body FOLLOWS its two entry points: tests/test_conv0_cases.py reads
+// the refusals, in order, from y2_conv0_fwd onwards.
+static int conv0_fwd_impl(const float* x_nchw, const float* w, const float* scale, const float* shift, float* y, float* y_pool, double* stats,
+                          int B, int H, int W, int Cin, int Cout, int ldy, int ldp, float slope, y2_stream_t stream, const float* pool_sign);
+
 extern "C" int y2_conv0_fwd(const float* x_nchw, const float* w, const float* scale, const float* shift,
                             float* y, float* y_pool, double* stats,
                             int B, int H, int W, int Cin, int Cout, int ldy, int ldp, float slope, y2_stream_t stream) {
+    return conv0_fwd_impl(x_nchw, w, scale, shift, y, y_pool, stats, B, H, W, Cin, Cout, ldy, ldp, slope, stream, nullptr);
+}
+
+extern "C" int y2_conv0_fwd_sel(const float* x_nchw, const float* w, const float* gamma, float* z, float* z_sel, double* stats,
+                                int B, int H, int W, int Cin, int Cout, int ldz, int ldzs, y2_stream_t stream) {
+    return (gamma != nullptr && z != nullptr && z_sel != nullptr) ? conv0_fwd_impl(x_nchw, w, nullptr, nullptr, z, z_sel, stats, B, H, W, Cin, Cout, ldz, ldzs, 1.f, stream, gamma)
+                                                                  : Y2_EINVAL;
+}
+
+static int conv0_fwd_impl(const float* x_nchw, const float* w, const float* scale, const float* shift, float* y, float* y_pool, double* stats,
+                          int B, int H, int W, int Cin, int Cout, int ldy, int ldp, float slope, y2_stream_t stream, const float* pool_sign) {
     if (x_nchw == nullptr || w == nullptr || (y == nullptr && y_pool == nullptr && stats == nullptr)) return Y2_EINVAL;
     if (B <= 0 || H <= 0 || W <= 0 || Cin < 1 || Cin > 4 || Cout < 1 || Cout > 64) return Y2_ENOSUP;
     if (y != nullptr && ldy < Cout) return Y2_EINVAL;
@@ -349,7 +393,7 @@ extern "C" int y2_conv0_fwd(const float* x_nchw, const float* w, const float* sc
     if (stats != nullptr && y2_det.on) return Y2_ENOSUP;      // deterministic mode: statistics come from y2_colstats_det
     Conv0Args a;
     a.x = x_nchw; a.w = w; a.scale = scale; a.shift = shift; a.y = y; a.y_pool = y_pool; a.stats = stats;
-    a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.ldy = ldy; a.ldp = ldp; a.slope = slope;
+    a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.ldy = ldy; a.ldp = ldp; a.slope = slope; a.pool_sign = pool_sign;
     a.tiles_y = y2_cdiv(H, TH); a.tiles_x = y2_cdiv(W, TW);
     a.ntiles = B * a.tiles_y * a.tiles_x;
     hipStream_t s = y2_s(stream);

@@ -50,6 +50,7 @@ struct ActArgs {
     float slope;
     const float* res; int ldr;     // optional residual added before the activation (model/resnet.py:59,101)
     y2_fastdiv d_wo, d_ho;         // exact 32-bit division by the (pooled) output width / height
+    float* z_sel; int ldzs;        // SEL: [B,H/2,W/2,C] (pixel stride ldzs), the z of each window's first maximal activation - the pixel the pool's gradient is routed to
 };
 
 __device__ __forceinline__ float act1(float z, float sc, float sh, float slope) {
@@ -70,7 +71,9 @@ __device__ __forceinline__ void act_decode(uint32_t p, const y2_fastdiv& d_wo, c
 }
 
 // one thread = CV channels (4 with 16-B accesses, or 1) of one pixel (POOL = false) or of one 2x2 window (POOL = true)
-template <bool POOL, int CV>
+// SEL (pooled blocks of the training forward): also stores z_sel = the window's z at its first maximal activation, the element that
+// bn_act_bwd_kernel<POOL> routes the pooled gradient to (same scan order, same strict comparison): pass 1 of the backward then reads z_sel, not z
+template <bool POOL, int CV, bool SEL = false>
 __global__ void bn_act_fwd_kernel(const ActArgs a, long long total) {
     const int Cg = a.C / CV;
     const int Wo = POOL ? a.W / 2 : a.W, Ho = POOL ? a.H / 2 : a.H;
@@ -85,20 +88,21 @@ __global__ void bn_act_fwd_kernel(const ActArgs a, long long total) {
     for (uint32_t p = (uint32_t)(tid / Cg); p < npix; p += pstep) {           // p = (b*Ho + yo)*Wo + xo
         int b = 0, yo = 0, xo = 0;
         if (need_yx) act_decode(p, a.d_wo, a.d_ho, Wo, Ho, b, yo, xo);
-        float pm[CV];
+        float pm[CV], bm[CV], zm[CV];
 #pragma unroll
         for (int q = 0; q < (POOL ? 4 : 1); ++q) {
             const int yy = POOL ? 2 * yo + (q >> 1) : yo, xx = POOL ? 2 * xo + (q & 1) : xo;
             const long long pix = need_yx ? ((long long)b * a.H + yy) * a.W + xx : (long long)p;
-            float v[CV];
+            float v[CV], zr[CV];
             if (CV == 4) {
                 const f32x4 zz = *reinterpret_cast<const f32x4*>(a.z + pix * a.ldz + c);
                 f32x4 rr = {0.f, 0.f, 0.f, 0.f};
                 if (a.res != nullptr) rr = *reinterpret_cast<const f32x4*>(a.res + pix * a.ldr + c);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const float u = zz[e] * sc[e] + sh[e] + rr[e]; v[e] = u > 0.f ? u : u * a.slope; }
+                for (int e = 0; e < 4; ++e) { const float u = zz[e] * sc[e] + sh[e] + rr[e]; v[e] = u > 0.f ? u : u * a.slope; zr[e] = zz[e]; }
             } else {
-                const float u = a.z[pix * a.ldz + c] * sc[0] + sh[0] + (a.res != nullptr ? a.res[pix * a.ldr + c] : 0.f);
+                zr[0] = a.z[pix * a.ldz + c];
+                const float u = zr[0] * sc[0] + sh[0] + (a.res != nullptr ? a.res[pix * a.ldr + c] : 0.f);
                 v[0] = u > 0.f ? u : u * a.slope;
             }
             if (a.y != nullptr) {
@@ -112,12 +116,20 @@ __global__ void bn_act_fwd_kernel(const ActArgs a, long long total) {
                 else a.y[o] = v[0];
             }
 #pragma unroll
-            for (int e = 0; e < CV; ++e) pm[e] = (q == 0) ? v[e] : fmaxf(pm[e], v[e]);
+            for (int e = 0; e < CV; ++e) {
+                if (SEL && (q == 0 || v[e] > bm[e])) { bm[e] = v[e]; zm[e] = zr[e]; }          // the backward's routing rule, operation for operation
+                pm[e] = (q == 0) ? v[e] : fmaxf(pm[e], v[e]);
+            }
         }
         if (POOL && a.y_pool != nullptr) {
             const long long o = (long long)p * a.ldp + a.poff + c;
             if (CV == 4) { f32x4 w = {pm[0], pm[1], pm[2], pm[3]}; *reinterpret_cast<f32x4*>(a.y_pool + o) = w; }
             else a.y_pool[o] = pm[0];
+        }
+        if (POOL && SEL) {
+            const long long o = (long long)p * a.ldzs + c;
+            if (CV == 4) { f32x4 w = {zm[0], zm[1], zm[2], zm[3]}; *reinterpret_cast<f32x4*>(a.z_sel + o) = w; }
+            else a.z_sel[o] = zm[0];
         }
     }
 }
@@ -904,27 +916,42 @@ extern "C" int y2_bn_finalize(const double* stats, double count, const float* ga
     return Y2_OK;
 }
 
-extern "C" int y2_bn_act_fwd_ex(const float* z, const float* scale, const float* shift, float slope, const float* residual, int ldr, float* y, float* y_pool,
-                                int B, int H, int W, int C, int ldz, int ldy, int coff, int ldp, int poff, int out_mode, y2_stream_t stream) {
+// z_sel / ldzs: the optional quarter-resolution output of the pooled form (y2_bn_act_fwd_sel)
+static int bn_act_fwd_impl(const float* z, const float* scale, const float* shift, float slope, const float* residual, int ldr, float* y, float* y_pool,
+                           int B, int H, int W, int C, int ldz, int ldy, int coff, int ldp, int poff, int out_mode, y2_stream_t stream, float* z_sel, int ldzs) {
     if (!z || (!y && !y_pool) || B <= 0 || H <= 0 || W <= 0 || C <= 0) return Y2_EINVAL;
     const bool pool = y_pool != nullptr;
+    if (z_sel != nullptr && (!pool || residual != nullptr || ldzs < C)) return Y2_EINVAL;
     if ((pool || out_mode == 1) && ((H & 1) || (W & 1))) return Y2_EINVAL;
     ActArgs a;
     a.z = z; a.scale = scale; a.shift = shift; a.y = y; a.y_pool = y_pool;
     a.B = B; a.H = H; a.W = W; a.C = C; a.ldz = ldz; a.ldy = ldy; a.coff = coff; a.ldp = ldp; a.poff = poff; a.out_mode = out_mode; a.slope = slope;
-    a.res = residual; a.ldr = ldr;
+    a.res = residual; a.ldr = ldr; a.z_sel = z_sel; a.ldzs = ldzs;
     if (residual != nullptr && ldr < C) return Y2_EINVAL;
-    const bool vec = (!residual || (!(ldr & 3) && y2_aligned16(residual))) && !(C & 3) && !(ldz & 3) && (!y || (!(ldy & 3) && !(coff & 3) && y2_aligned16(y))) && (!pool || (!(ldp & 3) && !(poff & 3) && y2_aligned16(y_pool))) && y2_aligned16(z);
+    const bool vec = (!residual || (!(ldr & 3) && y2_aligned16(residual))) && !(C & 3) && !(ldz & 3) && (!y || (!(ldy & 3) && !(coff & 3) && y2_aligned16(y))) && (!pool || (!(ldp & 3) && !(poff & 3) && y2_aligned16(y_pool))) && y2_aligned16(z) &&
+                     (!z_sel || (!(ldzs & 3) && y2_aligned16(z_sel)));
     const long long pix = (long long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W);
     if (pix >= 0x7fffffffLL || C > 8192) return Y2_ENOSUP;
     const long long total = pix * (vec ? C / 4 : C);
     const int grid = act_grid(total, vec ? C / 4 : C);
     a.d_wo = y2_make_fastdiv((uint32_t)(pool ? W / 2 : W)); a.d_ho = y2_make_fastdiv((uint32_t)(pool ? H / 2 : H));
     hipStream_t s = y2_s(stream);
-    if (pool) { if (vec) Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<true, 4>), dim3(grid), dim3(256), 0, s, a, total); else Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<true, 1>), dim3(grid), dim3(256), 0, s, a, total); }
+    if (z_sel != nullptr) { if (vec) Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<true, 4, true>), dim3(grid), dim3(256), 0, s, a, total); else Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<true, 1, true>), dim3(grid), dim3(256), 0, s, a, total); }
+    else if (pool) { if (vec) Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<true, 4>), dim3(grid), dim3(256), 0, s, a, total); else Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<true, 1>), dim3(grid), dim3(256), 0, s, a, total); }
     else { if (vec) Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<false, 4>), dim3(grid), dim3(256), 0, s, a, total); else Y2_LAUNCH("bn_act_fwd_kernel", 0.0, (bn_act_fwd_kernel<false, 1>), dim3(grid), dim3(256), 0, s, a, total); }
     Y2_LAUNCH_CHECK();
     return Y2_OK;
+}
+
+extern "C" int y2_bn_act_fwd_ex(const float* z, const float* scale, const float* shift, float slope, const float* residual, int ldr, float* y, float* y_pool,
+                                int B, int H, int W, int C, int ldz, int ldy, int coff, int ldp, int poff, int out_mode, y2_stream_t stream) {
+    return bn_act_fwd_impl(z, scale, shift, slope, residual, ldr, y, y_pool, B, H, W, C, ldz, ldy, coff, ldp, poff, out_mode, stream, nullptr, 0);
+}
+
+extern "C" int y2_bn_act_fwd_sel(const float* z, const float* scale, const float* shift, float slope, float* y_pool, float* z_sel,
+                                 int B, int H, int W, int C, int ldz, int ldp, int poff, int ldzs, y2_stream_t stream) {
+    if (!y_pool || !z_sel) return Y2_EINVAL;
+    return bn_act_fwd_impl(z, scale, shift, slope, nullptr, 0, nullptr, y_pool, B, H, W, C, ldz, 0, 0, ldp, poff, 0, stream, z_sel, ldzs);
 }
 
 // park / park_floats: with dz == NULL (pass 1 only), a caller-owned buffer that nothing reads before the caller's own next kernel writes it: the
@@ -932,8 +959,11 @@ extern "C" int y2_bn_act_fwd_ex(const float* z, const float* scale, const float*
 static int bn_act_bwd_impl(const float* z, const float* scale, const float* shift, const float* mean, const float* invstd, const float* gamma,
                            float slope, const float* dy_full, int ldf, int foff, int fmode, const float* dy_pool, int ldp, int poff,
                            const float* dy_full2, int ld2, const float* residual, int ldr, float* dres, int lddr,
-                           double* sums, float* dz, int ldd, int B, int H, int W, int C, int ldz, int has_bn, y2_stream_t stream, float* park, long long park_floats) {
+                           double* sums, float* dz, int ldd, int B, int H, int W, int C, int ldz, int has_bn, y2_stream_t stream, float* park, long long park_floats,
+                           const float* z_sel = nullptr, int ldzs = 0) {
     if (!z || (!dy_full && !dy_pool) || !sums || B <= 0 || H <= 0 || W <= 0 || C <= 0) return Y2_EINVAL;      // dz == NULL: the sums only (pass 1)
+    // z_sel (y2_bn_act_bwd_sel): a pooled gradient only, batch statistics - pass 1 reads one pre-activation per window
+    if (z_sel != nullptr && (!dy_pool || dy_full || dy_full2 || residual || has_bn != 1 || ldzs < C)) return Y2_EINVAL;
     if (dz == nullptr && dres != nullptr) return Y2_EINVAL;
     if (has_bn < 0 || has_bn > 2 || (has_bn && (!mean || !invstd || !gamma))) return Y2_EINVAL;
     const bool pool = dy_pool != nullptr;
@@ -946,7 +976,8 @@ static int bn_act_bwd_impl(const float* z, const float* scale, const float* shif
     a.slope = slope; a.n = (double)B * H * W; a.has_bn = has_bn;
     a.dy_full2 = dy_full2; a.ld2 = ld2; a.res = residual; a.ldr = ldr; a.dres = dres; a.lddr = lddr;
     const bool vec = (!dy_full2 || (!(ld2 & 3) && y2_aligned16(dy_full2))) && (!residual || (!(ldr & 3) && y2_aligned16(residual))) && (!dres || (!(lddr & 3) && y2_aligned16(dres))) && !(C & 3) && !(ldz & 3) && (!dz || (!(ldd & 3) && y2_aligned16(dz))) && y2_aligned16(z) &&
-                     (!dy_full || (!(ldf & 3) && !(foff & 3) && y2_aligned16(dy_full))) && (!pool || (!(ldp & 3) && !(poff & 3) && y2_aligned16(dy_pool)));
+                     (!dy_full || (!(ldf & 3) && !(foff & 3) && y2_aligned16(dy_full))) && (!pool || (!(ldp & 3) && !(poff & 3) && y2_aligned16(dy_pool))) &&
+                     (!z_sel || (!(ldzs & 3) && y2_aligned16(z_sel)));
     const int Cg = vec ? C / 4 : C;
     const long long pix = (long long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W);
     if (pix >= 0x7fffffffLL) return Y2_ENOSUP;
@@ -968,7 +999,7 @@ static int bn_act_bwd_impl(const float* z, const float* scale, const float* shif
     };
     const long long opix = pix;      // pooled gradient: one pixel per window
     const bool aliased = dz != nullptr && (overlaps(z, npix * ldz) || overlaps(dy_full, (fmode == 1 ? npix / 4 : npix) * (long long)ldf) || overlaps(dy_pool, opix * ldp) ||
-                                           overlaps(dy_full2, npix * ld2) || overlaps(residual, npix * ldr) || overlaps(dres, npix * lddr));
+                                           overlaps(dy_full2, npix * ld2) || overlaps(residual, npix * ldr) || overlaps(dres, npix * lddr) || overlaps(z_sel, opix * ldzs));
     a.block_partial = (dz != nullptr && !aliased && !y2_det.on && ldd == C && grid > 16 && (long long)grid * 2 * C <= npix * ldd) ? dz : nullptr;
     if (dz == nullptr && park != nullptr && !y2_det.on && grid > 16 && (long long)grid * 2 * C <= park_floats && y2_aligned16(park)) a.block_partial = park;
     const long long prow = (long long)grid * 256 / Cg;            // rows of per-thread partials (grid * 256 is a multiple of Cg)
@@ -976,9 +1007,16 @@ static int bn_act_bwd_impl(const float* z, const float* scale, const float* shif
         if ((size_t)prow * 2 * C * sizeof(float) > y2_det.bytes || prow > 0x7fffffffLL) return Y2_EINVAL;
         a.partial = y2_det.ws;
     }
+    // Pass 1 from z_sel is the UN-pooled pass 1 over the quarter-resolution maps (z_sel, dy_pool): the pooled kernel's thread-to-(window, channel group)
+    // mapping, grid and loop order (`total` counts windows either way), its sum without the three zero terms per window.
+    ActBwdArgs a1 = a;
+    if (z_sel != nullptr) {
+        a1.z = z_sel; a1.ldz = ldzs; a1.dy_full = dy_pool; a1.ldf = ldp; a1.foff = poff; a1.fmode = 0; a1.dy_pool = nullptr; a1.H = H / 2; a1.W = W / 2;
+    }
 #define Y2_BWD(POOL, CV)                                                                                             \
     do {                                                                                                             \
-        Y2_LAUNCH("bn_act_bwd_kernel", 0.0, (bn_act_bwd_kernel<POOL, CV, false>), dim3(grid), dim3(256), lds, s, a, total);            \
+        if (z_sel != nullptr) Y2_LAUNCH("bn_act_bwd_kernel", 0.0, (bn_act_bwd_kernel<false, CV, false>), dim3(grid), dim3(256), lds, s, a1, total);            \
+        else Y2_LAUNCH("bn_act_bwd_kernel", 0.0, (bn_act_bwd_kernel<POOL, CV, false>), dim3(grid), dim3(256), lds, s, a, total);            \
         if (a.partial != nullptr) {                                                                                  \
             const int rc_ = y2_det_reduce_f32(a.partial, (int)prow, (long long)2 * C, (long long)2 * C, sums, nullptr, s);            \
             if (rc_ != Y2_OK) return rc_;                                                                            \
@@ -1000,6 +1038,14 @@ extern "C" int y2_bn_act_bwd_ex(const float* z, const float* scale, const float*
                                 double* sums, float* dz, int ldd, int B, int H, int W, int C, int ldz, int has_bn, y2_stream_t stream) {
     return bn_act_bwd_impl(z, scale, shift, mean, invstd, gamma, slope, dy_full, ldf, foff, fmode, dy_pool, ldp, poff, dy_full2, ld2, residual, ldr, dres, lddr,
                            sums, dz, ldd, B, H, W, C, ldz, has_bn, stream, nullptr, 0);
+}
+
+extern "C" int y2_bn_act_bwd_sel(const float* z, const float* z_sel, int ldzs, const float* scale, const float* shift, const float* mean, const float* invstd,
+                                 const float* gamma, float slope, const float* dy_pool, int ldp, int poff, double* sums, float* dz, int ldd,
+                                 int B, int H, int W, int C, int ldz, y2_stream_t stream) {
+    if (!z_sel) return Y2_EINVAL;
+    return bn_act_bwd_impl(z, scale, shift, mean, invstd, gamma, slope, nullptr, 0, 0, 0, dy_pool, ldp, poff, nullptr, 0, nullptr, 0, nullptr, 0,
+                           sums, dz, ldd, B, H, W, C, ldz, 1, stream, nullptr, 0, z_sel, ldzs);
 }
 
 extern "C" long long y2_wino6_tiles(int32_t B, int32_t H, int32_t W) {

@@ -51,6 +51,11 @@ GRAPH_FORK = {'1': True, '0': False}.get(os.environ.get('Y2_GRAPH_FORK', 'auto')
 GRAD_F43 = os.environ.get('Y2_GRAD_F43', '1') != '0'        # offer Winograd F(4x4,3x3) to the data gradients of the deep layers (A/B)
 FUSE_WINO6 = os.environ.get('Y2_FUSE_WINO6', '1') != '0'      # 0: BatchNorm-backward pass 2 always writes dz and the 4x4-tile transforms read it (A/B; csrc/train.hip: bn_bwd_wino6_kernel)
 FUSE_CONV0 = os.environ.get('Y2_FUSE_CONV0', '1') != '0'      # 0: materialise the first layer's dz and run the two-kernel form (A/B runs)
+# Pooled blocks without a full-resolution consumer (layers1.0 / .2 / .6 / .10) keep z_sel, the one pre-activation per 2x2 window that the pool selects
+# (DESIGN.md 3.4): pass 1 of their BatchNorm backward reads it instead of z.  '0': off (A/B); '1': every block takes its best producer of z_sel;
+# 'act': every block takes the activation kernel's (y2_bn_act_fwd_sel).  Producers: the first layer's convolution (y2_conv0_fwd_sel), the activation
+# kernel for every other block.
+POOL_SEL = {'0': False, '1': True, 'act': 'act'}[os.environ.get('Y2_POOL_SEL', '1')]
 DEBUG_TAP = None        # debugging hook: callable(block name, dz, dx) invoked per block of the Darknet backward
 
 SYNC_POSITIVES = True   # data parallel: all-reduce the positive count so the cls mean is over the global batch
@@ -143,7 +148,7 @@ def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=No
 class _Block(object):
     """One conv block of the forward pass: geometry + saved tensors for backward."""
     __slots__ = ('mod', 'name', 'x', 'ldx', 'H', 'W', 'cin', 'cout', 'k', 'z', 'scale', 'shift', 'mean', 'invstd', 'pool',
-                 'out_full', 'out_pool', 'out_ld', 'out_off', 'out_mode', 'has_bn', 'slope', 'first', 'wino_v', 'eff')
+                 'out_full', 'out_pool', 'out_ld', 'out_off', 'out_mode', 'has_bn', 'slope', 'first', 'wino_v', 'eff', 'z_sel')
 
 
 PRUNE_OPERANDS = os.environ.get('Y2_PRUNE_OPERANDS', '1') != '0'      # 0: a captured step derives all four operand forms of every layer (A/B)
@@ -375,7 +380,17 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
         z = _new(dev, B, h, w, cout)
         stats = arena.take(cout) if (blk.has_bn and not frozen) else None
         estats = arena.epilogue(stats)          # statistics accumulated by the convolution's epilogue (atomics)
-        if first:
+        # pooled, nothing reads the full-resolution activation, batch statistics: keep the window's selected pre-activation z_sel for the backward's pass 1
+        # (the backward takes it only where the block's gradient turns out to be the pooled one alone: _decide_bwd).  Who writes it: the convolution
+        # where its kernel can (the sign of gamma is known before the statistics are) - the activation pass then reads z_sel, a quarter of z - else
+        # the activation kernel, which reads z anyway.
+        sel = bool(POOL_SEL and pool and out_full is None and not want_full and blk.has_bn and not frozen and not _hip.DETERMINISTIC and not (h & 1) and not (w & 1))
+        blk.z_sel = _new(dev, B, h // 2, w // 2, cout) if sel else None
+        sel_conv = sel and POOL_SEL is True and first
+        if sel_conv:
+            _hip.check(L.y2_conv0_fwd_sel(_hip.ptr(xin), _hip.ptr(e.w), _hip.ptr(e.gamma), _hip.ptr(z), _hip.ptr(blk.z_sel), _hip.ptr(estats),
+                                          B, h, w, cin, cout, cout, cout, st), 'y2_conv0_fwd_sel')
+        elif first:
             _hip.check(L.y2_conv0_fwd(_hip.ptr(xin), _hip.ptr(e.w), None, None, _hip.ptr(z), None, _hip.ptr(estats),
                                       B, h, w, cin, cout, cout, 0, 1.0, st), 'y2_conv0_fwd')
         elif mod in prepared:
@@ -406,8 +421,15 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
             y_full, out_ld, out_off = _new(dev, B, h, w, cout), cout, 0
         if pool:
             y_pool = _new(dev, B, h // 2, w // 2, cout)
-        _hip.check(L.y2_bn_act_fwd(_hip.ptr(z), _hip.ptr(blk.scale), _hip.ptr(blk.shift), blk.slope, _hip.ptr(y_full), _hip.ptr(y_pool),
-                                   B, h, w, cout, cout, out_ld, out_off, cout, 0, out_mode, st), 'y2_bn_act_fwd')
+        if sel_conv:          # act(z_sel) IS the pooled activation: an un-pooled pass over the quarter-resolution map
+            _hip.check(L.y2_bn_act_fwd(_hip.ptr(blk.z_sel), _hip.ptr(blk.scale), _hip.ptr(blk.shift), blk.slope, _hip.ptr(y_pool), None,
+                                       B, h // 2, w // 2, cout, cout, cout, 0, 0, 0, 0, st), 'y2_bn_act_fwd')
+        elif sel:
+            _hip.check(L.y2_bn_act_fwd_sel(_hip.ptr(z), _hip.ptr(blk.scale), _hip.ptr(blk.shift), blk.slope, _hip.ptr(y_pool), _hip.ptr(blk.z_sel),
+                                           B, h, w, cout, cout, cout, 0, cout, st), 'y2_bn_act_fwd_sel')
+        else:
+            _hip.check(L.y2_bn_act_fwd(_hip.ptr(z), _hip.ptr(blk.scale), _hip.ptr(blk.shift), blk.slope, _hip.ptr(y_full), _hip.ptr(y_pool),
+                                       B, h, w, cout, cout, out_ld, out_off, cout, 0, out_mode, st), 'y2_bn_act_fwd')
         blk.out_full, blk.out_pool, blk.out_ld, blk.out_off, blk.out_mode = y_full, y_pool, out_ld, out_off, out_mode
         blocks.append(blk)
         return blk, y_full, y_pool
@@ -458,9 +480,10 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
     return cur
 
 
-# what _decide_bwd reads of one saved block.  ud_ok: its prepared data-gradient operands allow the Winograd forms (None: none prepared); full / pooled: _routes
-_Geo = collections.namedtuple('_Geo', 'H W cin cout k ldx first has_v padded ud_ok full pooled')
-_Plan = collections.namedtuple('_Plan', 'wgrad zero final fuse0 fused6 problem')
+# what _decide_bwd reads of one saved block.  ud_ok: its prepared data-gradient operands allow the Winograd forms (None: none prepared); full / pooled: _routes;
+# has_sel: the forward kept the block's z_sel
+_Geo = collections.namedtuple('_Geo', 'H W cin cout k ldx first has_v padded ud_ok full pooled has_sel', defaults=(False,))
+_Plan = collections.namedtuple('_Plan', 'wgrad zero final fuse0 fused6 problem sel', defaults=(False,))
 
 
 def _routes(names, pools, n1, c_pt):
@@ -492,15 +515,17 @@ def _decide_bwd(geo, B, dev, need_dx=False):
     wgrad: _hip.wgrad_choice (0, 1, 2), None = unknown: it resolves at its launch (measured there), and what is prepared for it is right for any
     outcome - dz is materialised, nothing is fused, the target is zero filled on the weight gradient's stream; zero: the target is in the step's one
     zero fill; final: the target IS the gradient tensor (no unpack pass); fuse0: the first layer forms dz inside its weight gradient - no dz tensor
-    (1.4 GB at batch 64), no second pass; fused6: the (6, tile) data-gradient choice of a block that takes y2_bn_act_bwd_wino6, else None."""
+    (1.4 GB at batch 64), no second pass; fused6: the (6, tile) data-gradient choice of a block that takes y2_bn_act_bwd_wino6, else None; sel: pass 1 of the
+    BatchNorm backward reads the block's z_sel (y2_bn_act_bwd_sel): its only gradient is the pooled one."""
     plans = []
     for g in geo:
         cop = (g.cout + 3) // 4 * 4
+        sel = bool(g.has_sel and g.pooled and g.full is None)
         if g.first:
             small = g.cin <= 3 and g.cout <= 64          # y2_conv0_wgrad: writes the gradient's own layout, accumulating
             # (model/yolo2.py:78-79: conv + pool, nothing below it needs a data gradient: only the weight gradient reads dz - from (z, dy_pool) and the pass-1 sums)
             fuse0 = bool(FUSE_CONV0 and small and g.full is None and g.pooled and not (g.H & 1) and not (g.W & 15) and B * g.H * g.W * g.cout * 4 < 0xffff0000 and not need_dx)
-            plans.append(_Plan(0, small, small, fuse0, None, None))
+            plans.append(_Plan(0, small, small, fuse0, None, None, sel))
             continue
         wgrad = _hip.wgrad_choice(B, g.H, g.W, g.cin, g.ldx, cop, cop, g.k, g.has_v, dev)
         # weight AND data gradient KNOWN to run the 4x4-tile forms: y2_bn_act_bwd_wino6 writes their two transforms instead of dz
@@ -510,7 +535,7 @@ def _decide_bwd(geo, B, dev, need_dx=False):
             problem = _problem(B, g.H, g.W, cop, cop, g.cin, g.k, g.cin)          # described once: the launch fills in its pointers
             hit = _hip.autotune_conv(problem, dev, f43=True if _f43_offered(g.ud_ok, cop, g.H, g.W) else None, wino_eligible=g.ud_ok, peek=True)
             fused6 = tuple(hit) if (hit is not None and hit[0] == 6) else None
-        plans.append(_Plan(wgrad, wgrad == 0, g.k == 1 and cop == g.cout and not g.padded, False, fused6, problem if fused6 else None))      # (final: [cout][1][cin] IS the state_dict layout)
+        plans.append(_Plan(wgrad, wgrad == 0, g.k == 1 and cop == g.cout and not g.padded, False, fused6, problem if fused6 else None, sel))      # (final: [cout][1][cin] IS the state_dict layout)
     return plans
 
 
@@ -534,7 +559,7 @@ def _darknet_bwd(ctx, dout):
     routes, full, pooled = _routes([b.name for b in blocks], [b.pool for b in blocks], len(dnn._blocks()[0]), c_pt)
     need_dx = bool(getattr(ctx, 'need_dx', False))
     plans = _decide_bwd([_Geo(b.H, b.W, b.cin, b.cout, b.k, b.ldx, b.first, b.wino_v is not None, b.eff.padded,
-                              ctx.prepared[b.mod]['ud_ok'] if (not b.first and b.mod in ctx.prepared) else None, full[i], pooled[i]) for i, b in enumerate(blocks)], B, str(dev), need_dx)
+                              ctx.prepared[b.mod]['ud_ok'] if (not b.first and b.mod in ctx.prepared) else None, full[i], pooled[i], b.z_sel is not None) for i, b in enumerate(blocks)], B, str(dev), need_dx)
     order = list(range(n - 1, -1, -1))
     main = torch.cuda.current_stream(dev)
     # (under capture only a StepPlan - which joins the side stream before it ends a graph segment, ctx.join - may fork: an unjoined stream fails the capture)
@@ -606,6 +631,9 @@ def _darknet_bwd(ctx, dout):
                                              _hip.ptr(e.gamma) if blk.has_bn else None, blk.slope, _hip.ptr(sf[0]), sf[1], sf[2], _hip.ptr(sums),
                                              _hip.ptr(fused6[0]), _hip.ptr(fused6[1]), None, 0, B, h, w, cout, cout,
                                              (2 if ctx.frozen else 1) if blk.has_bn else 0, st), 'y2_bn_act_bwd_wino6')
+        elif plan.sel:
+            _hip.check(L.y2_bn_act_bwd_sel(_hip.ptr(blk.z), _hip.ptr(blk.z_sel), cout, _hip.ptr(blk.scale), _hip.ptr(blk.shift), _hip.ptr(blk.mean), _hip.ptr(blk.invstd),
+                                           _hip.ptr(e.gamma), blk.slope, _hip.ptr(sp), cout, 0, _hip.ptr(sums), _hip.ptr(dz), cop, B, h, w, cout, cout, st), 'y2_bn_act_bwd_sel')
         else:
             _hip.check(L.y2_bn_act_bwd(_hip.ptr(blk.z), _hip.ptr(blk.scale), _hip.ptr(blk.shift), _hip.ptr(blk.mean), _hip.ptr(blk.invstd),
                                        _hip.ptr(e.gamma) if blk.has_bn else None, blk.slope,
@@ -725,7 +753,7 @@ def _darknet_bwd(ctx, dout):
                     src_pool[j] = dx
                 else:
                     src_full[j] = (dx, cin, off, mode)
-        blk.z = None   # free as we go
+        blk.z = blk.z_sel = None   # free as we go
     sink.hand_affine(sums_arena, affine_grads, st)          # fp64 sums -> fp32, one launch
     flush_weight_grads()
     L.y2_prof_set_tag(0)
