@@ -352,6 +352,36 @@ int y2_warp_affine_images(const uint8_t* src, const int64_t* src_offset, const i
                           uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
                           int32_t B, int32_t max_h, int32_t max_w, int32_t fill, y2_stream_t stream);
 
+/* The test-time `fixed` resize of the data pipeline (transform/resize/image.py:36-46: cv2.warpAffine(image, [[s, 0, 0], [0, s, 0]], (W, H), flags) -
+ * the picture scaled by s into the top-left of a zero canvas, INTER_AREA (which warpAffine runs as INTER_LINEAR) when s < 1, INTER_CUBIC otherwise)
+ * fused with BGR2RGB, ToTensor and Normalize, for a ragged batch of uint8 images in ONE launch, IN PLACE of y2_collate_images: packed source images
+ * straight to out [B][3][H][W] fp32, no uint8 intermediate.
+ * src / offset: as y2_collate_images.  geom [B][4] int32: {row_stride_bytes, src_h, src_w, mode}, mode 0 = linear, 1 = cubic.  inv [B][6] double: A,
+ * the INVERSE map, destination (x, y) -> source (A0 x + A1 y + A2, A3 x + A4 y + A5), as y2_warp_affine_images takes it (any affine map is accepted,
+ * not only a scale).  lut [3][256] fp32, flags bit 0 (BGR2RGB) and out: as y2_collate_images.  The level outside the source is 0.
+ * Coordinates, both modes: those of y2_warp_affine_images above (adelta, bdelta, X0, Y0 with 10 fractional bits, X = (X0 + adelta) >> 5, sx = X >> 5,
+ * ax = X & 31, sy and ay alike, sx and sy saturated to [-32768, 32767]).
+ * Mode 0: the bilinear level of y2_warp_affine_images with fill 0 and no flip; out[b][c][y][x] = lut[c][that level] of the channel the flag selects -
+ * bit for bit what y2_warp_affine_images into an H x W canvas followed by the table gives.
+ * Mode 1 - cv2.warpAffine for 8-bit images, INTER_CUBIC, BORDER_CONSTANT 0, restated.  Taps: rows sy - 1 .. sy + 2 x columns sx - 1 .. sx + 2; a tap
+ * outside [0, src_h) x [0, src_w) reads 0.  One-dimensional coefficients of a fraction a / 32, fp32, every operation rounded separately, A = -0.75f,
+ * t = a * (1.f / 32.f):
+ *   c0 = ((A (t + 1) - 5 A)(t + 1) + 8 A)(t + 1) - 4 A;  c1 = ((A + 2) t - (A + 3)) t t + 1;  c2 = ((A + 2)(1 - t) - (A + 3))(1 - t)(1 - t) + 1;
+ *   c3 = 1.f - c0 - c1 - c2   (left to right).
+ * Weights w[i][j] = saturate_int16(rint((cy[i] * cx[j]) * 32768.f)), i the row and j the column of the tap.  When they do not sum to 32768 the
+ * difference d = sum - 32768 is taken out of ONE of the four central weights (i, j in {1, 2}): start with min = max = [1][1], visit [1][1], [1][2],
+ * [2][1], [2][2]; an element strictly below the current minimum becomes the minimum, else one strictly above the current maximum becomes the maximum;
+ * d < 0: max -= d, d > 0: min -= d (the result is not narrowed to 16 bits again: a = 0 on both axes gives 0, 32768, 0, 0 - the identity map is an
+ * exact copy).  Per channel level = clamp((sum of p w + 16384) >> 15, 0, 255) (arithmetic shift).  The weights are computed per pixel by the one
+ * function of csrc/fixed.h on device and host: bit-identical.
+ * This is OpenCV's recipe restated from its description; agreement with a real cv2.warpAffine is UNVERIFIED (cv2 is not available to the tests).
+ * H, W and all source dimensions in [1, Y2_WARP_MAX_DIM]; |A0|, |A1|, |A3|, |A4| <= 4 and |A2|, |A5| <= 2^19.  The tables are DEVICE memory: the
+ * device entry point cannot check them (utils.data.to_device and the host function do); it rounds through saturating clamps, forms the sums in 64
+ * bits and loads only from positions clamped into the image the table names (the value of a tap outside is dropped).  B == 0: nothing is launched;
+ * B > 65535: Y2_ENOSUP.  16-byte stores when W % 4 == 0 and out is 16-byte aligned, 4-byte stores otherwise.  Never allocates, never synchronises. */
+int y2_fixed_images(const uint8_t* src, const int64_t* offset, const int32_t* geom, const double* inv, const float* lut,
+                    int32_t B, int32_t H, int32_t W, int32_t flags, float* out, y2_stream_t stream);
+
 /* The collate step WITH the colour jitter of the data pipeline (utils/data.py:120-121: resize, then transform_image - transform/image.py: RandomBlur,
  * BGR2HSV, RandomHue / RandomSaturation / RandomBrightness, HSV2RGB, RandomGamma - then ToTensor, Normalize) for a ragged batch in ONE launch, in
  * place of y2_collate_images.  src / offset / geom, B, H, W, flags and out mean exactly what they mean there (so it reads the output of
@@ -528,6 +558,11 @@ int y2_collate_images_host(const uint8_t* src, const int64_t* offset, const int3
 int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src_offset, const int32_t* src_geom, const double* inv,
                                uint8_t* dst, const int64_t* dst_offset, const int32_t* dst_geom,
                                int32_t B, int32_t max_h, int32_t max_w, int32_t fill);
+/* y2_fixed_images on host memory (utils.data.to_device on 'cpu'): the same arithmetic, bit-identical output.  The tables are checked first
+ * (offset >= 0, source dimensions in [1, Y2_WARP_MAX_DIM], row_stride_bytes >= 3 * src_w, mode 0 or 1, the ranges of A above; a NaN is out of
+ * range): Y2_EINVAL, nothing is written. */
+int y2_fixed_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const double* inv, const float* lut,
+                         int32_t B, int32_t H, int32_t W, int32_t flags, float* out);
 /* y2_collate_jitter_images on host memory (utils.data.to_device on 'cpu'): the same arithmetic, bit-identical output.  The tables are checked first
  * (those of y2_collate_images_host; kx and ky in 1 .. Y2_JITTER_MAX_BLUR, hsv 0 or 1, jitter[b][3] == 0, hsv_tab present when an image sets hsv):
  * Y2_EINVAL, nothing is written. */

@@ -145,6 +145,8 @@ SIGNATURES = {
     'y2_collate_images_host': [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_warp_affine_images': [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_warp_affine_images_host': [c_void_p] * 7 + [c_int, c_int, c_int, c_int],
+    'y2_fixed_images': [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    'y2_fixed_images_host': [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_collate_jitter_images': [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     'y2_collate_jitter_images_host': [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p],
     'y2_jpeg_probe_host': [c_void_p, ctypes.c_int64, c_void_p],
@@ -450,7 +452,7 @@ def kernel_hash():
     """sha256 (16 hex digits) of the kernel sources the library is built from; None when the sources are not there."""
     import glob
     import hashlib
-    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(_HERE, 'csrc', 'jpeg.h'), os.path.join(_HERE, 'csrc', 'kmeans.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
+    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip'))) + [os.path.join(_HERE, 'csrc', 'common.h'), os.path.join(_HERE, 'csrc', 'resample.h'), os.path.join(_HERE, 'csrc', 'jpeg.h'), os.path.join(_HERE, 'csrc', 'kmeans.h'), os.path.join(_HERE, 'csrc', 'fixed.h'), os.path.join(os.path.dirname(_HERE), 'include', 'yolo2_hip.h')]
     if len(files) < 3 or not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha256()

@@ -12,7 +12,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I$ROOT/incl
 pids=()
 for f in "$HERE"/*.hip; do
     o="$OBJ/$(basename "${f%.hip}").o"
-    if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/common.h" -nt "$o" ] || [ "$HERE/resample.h" -nt "$o" ] || { [ "$HERE/jpeg.h" -nt "$o" ] && grep -q '"jpeg.h"' "$f"; } || { [ "$HERE/kmeans.h" -nt "$o" ] && grep -q '"kmeans.h"' "$f"; } || [ "$ROOT/include/yolo2_hip.h" -nt "$o" ]; then
+    if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/common.h" -nt "$o" ] || [ "$HERE/resample.h" -nt "$o" ] || { [ "$HERE/jpeg.h" -nt "$o" ] && grep -q '"jpeg.h"' "$f"; } || { [ "$HERE/kmeans.h" -nt "$o" ] && grep -q '"kmeans.h"' "$f"; } || { [ "$HERE/fixed.h" -nt "$o" ] && grep -q '"fixed.h"' "$f"; } || [ "$ROOT/include/yolo2_hip.h" -nt "$o" ]; then
         extra="$(sed -n 's|^// y2-build-flags: ||p' "$f" | head -1)"          # per-file code generation options, stated in the source
         $HIPCC $FLAGS $extra -c "$f" -o "$o" &
         pids+=($!)

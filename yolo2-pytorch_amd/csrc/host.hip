@@ -1,6 +1,6 @@
 // host.hip — HOST-memory entry points of libyolo2_hip.so (include/yolo2_hip.h: y2_nms_host, y2_iou_matrix_host, y2_iou_pair_host,
 // y2_eval_match_host, y2_collate_images_host, y2_warp_affine_images_host, y2_collate_jitter_images_host, y2_jpeg_probe_host,
-// y2_jpeg_workspace_bytes, y2_jpeg_decode_images_host, y2_anchor_kmeans_host, y2_anchor_assign_host).
+// y2_jpeg_workspace_bytes, y2_jpeg_decode_images_host, y2_anchor_kmeans_host, y2_anchor_assign_host, y2_fixed_images_host).
 //
 // The reference calls utils.postprocess.nms on CPU tensors from its summary worker process (train.py:209, a child forked
 // after the GPU was initialised, which must never touch the device) and runs the utils.iou.torch unit tests on CPU tensors
@@ -18,6 +18,7 @@
 #include "resample.h"
 #include "jpeg.h"
 #include "kmeans.h"
+#include "fixed.h"
 
 namespace {
 
@@ -252,6 +253,14 @@ extern "C" int y2_warp_affine_images_host(const uint8_t* src, const int64_t* src
         }
     }
     return Y2_OK;
+}
+
+// y2_fixed_images on host memory: csrc/fixed.h's fx_images_host (the table checks, then fixed.hip's kernel serially, the same arithmetic).
+static_assert(Y2_WARP_MAX_DIM == FX_MAX_DIM && Y2_OK == 0 && Y2_EINVAL == -1 && Y2_ENOSUP == -3, "include/yolo2_hip.h and csrc/fixed.h disagree");
+
+extern "C" int y2_fixed_images_host(const uint8_t* src, const int64_t* offset, const int32_t* geom, const double* inv, const float* lut,
+                                    int32_t B, int32_t H, int32_t W, int32_t flags, float* out) {
+    return fx_images_host(src, offset, geom, inv, lut, B, H, W, flags, out);
 }
 
 // y2_collate_jitter_images on host memory (jitter.hip: collate_jitter_images_kernel, image by image instead of tile by tile).  The tables are readable

@@ -3,9 +3,24 @@
 `filter_visible` / `postprocess` keep the reference's signatures (one image, config-driven thresholds);
 `postprocess_batch` is the device-resident form of the same a20 -> a21 -> a22 chain for a whole
 batch: decode+softmax+max (y2_decode), threshold compaction (y2_filter_visible), rank + greedy NMS (y2_nms),
-with no host round trip between the stages.  The OpenCV capture / drawing CLI of the reference (detect.py:83-214)
-is out of scope.
+with no host round trip between the stages.
+
+`Detector` is the front and the back the reference's `Detect` class (detect.py:83-175) puts around them, for FILES: pictures -> utils.data.collate_images
+(`[transform] resize_test`: transform.resize.image, `rescale` or `fixed`) -> utils.data.to_device (one y2_collate_images or y2_fixed_images launch) ->
+the network and the chain above in a captured graph -> boxes in the pixels of each source picture (`to_source`).  `main` is the command line: a
+file or a directory of pictures in, annotated pictures and detections.tsv out.  Two deliberate deviations from the reference, both in `to_source`:
+the reference caches the scale of the FIRST frame (`self.scale`, right for a video and wrong for a directory of pictures) - here it is computed per
+picture; and it applies the `rescale` formula under `fixed` as well, which misplaces every box of a letterboxed picture - here the map is the inverse
+of the transform that was applied.  Camera and video input, the OpenCV window and the video writer stay out: they need cv2.
 """
+import argparse
+import configparser
+import inspect
+import logging
+import logging.config
+import os
+
+import numpy as np
 import torch
 
 import _hip
@@ -204,3 +219,198 @@ class GraphedDetector(object):
             self.static_x.copy_(x)
         self.graph.replay()
         return self.result
+
+
+def to_source(yx, record, rows, cols, height, width):
+    """Box corners `yx` [n, 2] in cells of the rows x cols head image -> pixels of the SOURCE picture (float32 numpy, unclipped).  `record`: the
+    picture's sample dict after its transform.resize.image transform; (height, width): the network input.
+    `rescale` (record['window'] = the whole src_h x src_w picture): yx * (src_h / rows, src_w / cols), the reference's detect.py:160-162.
+    `fixed` (record['fixed']): the picture was scaled by `scale` into the top-left of the canvas, so yx * (height / rows, width / cols) / scale - the
+    inverse of the transform that was applied (the reference applies the `rescale` formula here too, and caches the scale of its first frame:
+    both are deliberately not reproduced)."""
+    if 'fixed' in record:
+        scale = float(record['fixed']['scale'])
+        factor = (height / rows / scale, width / cols / scale)
+    else:
+        _, _, src_h, src_w = record['window']
+        factor = (src_h / rows, src_w / cols)
+    return np.asarray(yx, np.float32).reshape(-1, 2) * np.array(factor, np.float32)
+
+
+def parse_resize(config, method):
+    """`[transform] resize_test` -> the transform object, as the reference's transform.parse_transform: the dotted name is resolved with
+    utils.parse_attr and called with the config when it takes one argument, without arguments otherwise."""
+    if not isinstance(method, str):
+        return method
+    attr = utils.parse_attr(method)
+    return attr(config) if len(inspect.signature(attr).parameters) == 1 else attr()
+
+
+def image_options(config):
+    """(swap_rb, normalize) of `[transform] image_test` and `[transform] tensor`: what utils.data.collate_images takes.  The test path has no
+    jitter: a sequence other than nothing or BGR2RGB raises."""
+    import transform.image
+    jitter = transform.image.get_transform(config, config.get('transform', 'image_test', fallback='transform.image.BGR2RGB').split())
+    if jitter.active:
+        raise ValueError('[transform] image_test: the test path serves BGR2RGB only')
+    normalize = None
+    for name in config.get('transform', 'tensor', fallback='torchvision.transforms.ToTensor transform.image.Normalize').split():
+        if name == 'transform.image.Normalize':
+            plugin = transform.image.Normalize(config)
+            normalize = (plugin.mean, plugin.std)
+        elif name != 'torchvision.transforms.ToTensor':
+            raise ValueError('[transform] tensor: %s is not served by the level table (ToTensor and transform.image.Normalize are)' % name)
+    return jitter.swap_rb, normalize
+
+
+class Detector(object):
+    """Pictures in, boxes in source pixels out.  Reads `[image] size`, `[transform] resize_test` (transform.resize.image.Resize / Rescale / Fixed),
+    `[transform] image_test` / `tensor` (BGR2RGB, Normalize) and `[detect] fix` / `threshold` / `threshold_cls` / `overlap`.
+    dnn: a plugin on the GPU in eval mode with `forward_nhwc`; anchors: the (height, width) table in cells.
+    One GraphedDetector is captured per batch size and kept; to_device writes straight into its static input."""
+
+    def __init__(self, config, dnn, anchors, device=None):
+        import utils.data
+        self.config, self.dnn = config, dnn
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device.type == 'cuda' and device.index is None else device
+        self.anchors = anchors.to(self.device, torch.float32).contiguous()
+        self.height, self.width = (int(v) for v in config.get('image', 'size').split())
+        self.resize = parse_resize(config, config.get('transform', 'resize_test'))
+        self.swap_rb, self.normalize = image_options(config)
+        self.fix = config.getboolean('detect', 'fix')
+        self.kwargs = dict(fix=self.fix, threshold=config.getfloat('detect', 'threshold'), threshold_cls=config.getfloat('detect', 'threshold_cls'),
+                           overlap=config.getfloat('detect', 'overlap'))
+        utils.data.level_table(self.normalize, self.device)          # (its first call copies from pageable memory)
+        self._graphs = {}
+
+    def collate(self, images):
+        """(samples, batch): the sample dicts after the resize transform and the dict of utils.data.collate_images."""
+        import utils.data
+        samples = [dict(image=utils.data.read_image(image) if isinstance(image, (str, os.PathLike)) else image) for image in images]
+        return samples, utils.data.collate_images(samples, self.resize, self.height, self.width, self.swap_rb, self.normalize)
+
+    def __call__(self, images):
+        """images: uint8 [h, w, 3] BGR arrays, utils.data.JpegImage objects or paths.  Returns, per picture, None or (yx_min [n, 2], yx_max [n, 2],
+        cls [n], score [n]) as numpy arrays, the corners in pixels of that picture, unclipped, as the reference leaves them."""
+        import utils.data
+        if not len(images):
+            return []
+        samples, batch = self.collate(images)
+        B = len(samples)
+        with torch.cuda.device(self.device):
+            entry = self._graphs.get(B)
+            if entry is None:
+                x = utils.data.to_device(batch, self.device)['tensor']
+                with torch.no_grad():
+                    rows, cols = self.dnn.forward_nhwc(x).shape[1:3]
+                entry = self._graphs[B] = (GraphedDetector(self.dnn, self.anchors, x, static_input=True, **self.kwargs), int(rows), int(cols))
+            else:
+                utils.data.to_device(batch, self.device, out=entry[0].static_x)
+            graphed, rows, cols = entry
+            results = postprocess_batch(graphed.run(), self.fix, self.kwargs['threshold_cls'], to_host=True)
+        out = []
+        for record, result in zip(samples, results):
+            if result is None:
+                out.append(None)
+                continue
+            _, yx_min, yx_max, cls, score = result
+            out.append((to_source(yx_min.numpy(), record, rows, cols, self.height, self.width), to_source(yx_max.numpy(), record, rows, cols, self.height, self.width),
+                        cls.numpy().copy(), score.numpy().copy()))
+        return out
+
+
+PICTURES = ('.jpg', '.jpeg', '.png')
+VIDEOS = ('.avi', '.mp4', '.mkv', '.mov', '.mpg', '.mpeg', '.webm', '.flv', '.wmv')
+
+
+def list_pictures(path):
+    """The picture files of `-i`: the file itself, or the .jpg / .jpeg / .png files of a directory in sorted order.  A camera index or a video file
+    raises: both need cv2, which this workflow does without."""
+    try:
+        int(path)
+    except ValueError:
+        pass
+    else:
+        raise NotImplementedError('-i %s is a camera: capture needs cv2 (OpenCV), which is not available; give a picture file or a directory of pictures' % path)
+    path = os.path.expanduser(os.path.expandvars(path))
+    if os.path.splitext(path)[1].lower() in VIDEOS:
+        raise NotImplementedError('-i %s is a video: reading it needs cv2 (OpenCV), which is not available; give a picture file or a directory of pictures' % path)
+    if os.path.isdir(path):
+        return [os.path.join(path, name) for name in sorted(os.listdir(path)) if os.path.splitext(name)[1].lower() in PICTURES]
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    return [path]
+
+
+def build_detector(config, category):
+    """The newest checkpoint of the model directory, its plugin on the current GPU, and the Detector around it (detect.py:84-106)."""
+    import utils.train
+    anchors = torch.from_numpy(utils.get_anchors(config)).contiguous()
+    path, step, epoch = utils.train.load_model(utils.get_model_dir(config))
+    state_dict = torch.load(path, map_location='cpu')
+    dnn = utils.parse_attr(config.get('model', 'dnn'))(model.ConfigChannels(config, state_dict), anchors, len(category))
+    dnn.load_state_dict(state_dict)
+    return Detector(config, dnn.eval().cuda(), anchors)
+
+
+def main(argv=None, detector=None):
+    """detect.py -c config.ini -i pictures/ -o out/: every picture of the input, `-b` at a time, through the Detector; per picture the annotated
+    copy (rectangles, a colour per class; no text: there is no font renderer without cv2) written with Pillow under its own name, and one
+    detections.tsv (file, class name, score, ymin, xmin, ymax, xmax in source pixels).  detector: an object called like Detector (tests)."""
+    from PIL import Image
+
+    import utils.data
+    import utils.visualize
+    args = make_args(argv)
+    config = configparser.ConfigParser()
+    utils.load_config(config, args.config)
+    for cmd in args.modify:
+        utils.modify_config(config, cmd)
+    if args.logging:
+        import yaml
+        with open(os.path.expanduser(os.path.expandvars(args.logging)), 'r') as f:
+            logging.config.dictConfig(yaml.safe_load(f))
+    paths = list_pictures(args.input)
+    cache_dir = utils.get_cache_dir(config)
+    category = utils.get_category(config, cache_dir if os.path.exists(cache_dir) else None)
+    draw_bbox = utils.visualize.DrawBBox(category, colors=args.colors, thickness=args.thickness)
+    if detector is None:
+        detector = build_detector(config, category)
+    output = os.path.expanduser(os.path.expandvars(args.output))
+    os.makedirs(output, exist_ok=True)
+    with open(os.path.join(output, 'detections.tsv'), 'w') as tsv:
+        tsv.write('file\tclass\tscore\tymin\txmin\tymax\txmax\n')
+        for first in range(0, len(paths), args.batch_size):
+            batch = paths[first:first + args.batch_size]
+            for path, result in zip(batch, detector(batch)):
+                image = utils.data.imread_host(path)          # the pictures stay on the host: drawing is a few slices per box
+                name = os.path.basename(path)
+                if result is not None:
+                    yx_min, yx_max, cls, score = result
+                    image = draw_bbox(image, yx_min.astype(np.int64), yx_max.astype(np.int64), cls)
+                    for (ymin, xmin), (ymax, xmax), c, s in zip(yx_min.tolist(), yx_max.tolist(), cls.tolist(), score.tolist()):
+                        tsv.write('%s\t%s\t%.6f\t%.2f\t%.2f\t%.2f\t%.2f\n' % (name, category[int(c)], s, ymin, xmin, ymax, xmax))
+                Image.fromarray(np.ascontiguousarray(image[..., ::-1])).save(os.path.join(output, name))
+            logging.info('%d / %d pictures', min(first + args.batch_size, len(paths)), len(paths))
+    return 0
+
+
+def make_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('-c', '--config', nargs='+', default=['config.ini'], help='config file')
+    parser.add_argument('-m', '--modify', nargs='+', default=[], help='modify config')
+    parser.add_argument('-i', '--input', required=True, help='a picture file or a directory of .jpg / .jpeg / .png files')
+    parser.add_argument('-o', '--output', required=True, help='output directory: the annotated pictures and detections.tsv')
+    parser.add_argument('-b', '--batch_size', default=16, type=int)
+    parser.add_argument('--thickness', default=3, type=int)
+    parser.add_argument('--colors', nargs='+', default=[])
+    parser.add_argument('--logging', default=None, help='logging config (yaml), optional')
+    args = parser.parse_args(argv)
+    if args.batch_size < 1:
+        parser.error('--batch_size must be positive')
+    return args
+
+
+if __name__ == '__main__':
+    main()

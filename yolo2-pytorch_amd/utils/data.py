@@ -24,7 +24,11 @@ else is decoded on the host as before.  `Collate` packs the pixels of host-decod
 `offset` / `geom` rows that point at space reserved BEHIND them, which only exists on the device; the files' bytes travel as `jpeg`, `jpeg_offset`,
 `jpeg_desc`.  `to_device` allocates the whole pixel buffer, copies the host part and the files (about a tenth of the pixel bytes), launches
 y2_jpeg_decode_images in front of the launches above and adds `jpeg_status` without looking at it.  A batch without a JpegImage is untouched by all
-this: the same keys, the same bytes, the same launches."""
+this: the same keys, the same bytes, the same launches.
+
+`collate_images` is the label-less counterpart of `Collate.__call__` for the test path (detect.Detector): pictures through a transform of
+transform.resize.image, packed by the same code (`pack_images`).  With the `fixed` resize it adds `fixed_geom` / `fixed_inv`, and `to_device` launches
+y2_fixed_images (the aspect-preserving warp, linear or cubic, fused with the channel swap and the level table) IN PLACE of y2_collate_images."""
 import copy
 import os
 import pickle
@@ -222,7 +226,74 @@ def check_jitter(jitter, hsv_tab, lut_b, B):
         raise ValueError('jitter: image %d: blur size outside 1 .. %d, hsv not 0 / 1 or hsv without hsv_tab (jitter %s)' % (b, limit, jitter[b].tolist()))
 
 
-ROT_ROW_ALIGN, ROT_IMAGE_ALIGN = 16, 64      # the layout of the rotated images is Collate's: rows and images start where the warp kernel's 12-byte stores are aligned
+def check_fixed(offset, fixed_geom, fixed_inv, nbytes):
+    """The tables of y2_fixed_images against the byte buffer they index (host arrays): every image inside the buffer, dimensions, modes and matrix
+    entries in the ranges of include/yolo2_hip.h."""
+    offset, geom, inv = np.asarray(offset, np.int64), np.asarray(fixed_geom, np.int64), np.asarray(fixed_inv, np.float64)
+    B = len(geom)
+    if geom.ndim != 2 or geom.shape[1] != 4 or offset.shape != (B,) or inv.shape != (B, 6):
+        raise ValueError('fixed: offset must be [B], fixed_geom [B, 4] and fixed_inv [B, 6] (got %s, %s and %s)' % (offset.shape, geom.shape, inv.shape))
+    stride, src_h, src_w, mode = geom.T
+    limit = _hip.WARP_MAX_DIM
+    with np.errstate(invalid='ignore'):
+        in_range = (np.abs(inv[:, [0, 1, 3, 4]]) <= 4).all(1) & (np.abs(inv[:, [2, 5]]) <= 2 ** 19).all(1)          # (a NaN is out of range)
+    bad = ((offset < 0) | (src_h < 1) | (src_h > limit) | (src_w < 1) | (src_w > limit) | (stride < 3 * src_w) | ((mode != 0) & (mode != 1))
+           | (offset + (src_h - 1) * stride + 3 * src_w > nbytes) | ~in_range)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError('fixed: image %d: image outside its buffer, mode not 0 / 1 or matrix out of range (offset %d of %d bytes, fixed_geom %s, fixed_inv %s)'
+                         % (b, offset[b], nbytes, geom[b].tolist(), inv[b].tolist()))
+
+
+ROT_ROW_ALIGN, ROT_IMAGE_ALIGN = 16, 64     # the layout of the rotated images is Collate's: rows and images start where the warp kernel's 12-byte stores are aligned
+
+
+def _window_row(data):
+    """Columns 3-7 of a sample's geometry row: the recorded window and flip; a sample of transform.resize.image.fixed shows its whole image."""
+    if 'window' not in data and 'fixed' in data:
+        h, w = data['image'].shape[:2]
+        return (0, 0, int(h), int(w), 0)
+    return tuple(data['window']) + (int(bool(data['flip'])),)
+
+
+def pack_images(samples):
+    """The images of prepared samples as the tables of y2_collate_images: (raw uint8 [n], offset int64 [B], geom int32 [B, 8], the size of the pixel
+    buffer in bytes, the JPEG tables as a dict).  Host-decoded pixels are packed back to back; JpegImage samples get rows that point at space reserved
+    behind them, which only exists on the device."""
+    offset = np.zeros(len(samples), np.int64)
+    geom = np.zeros((len(samples), 8), np.int32)
+    pos = 0
+    compressed = [b for b, data in enumerate(samples) if isinstance(data['image'], JpegImage)]
+    for b, data in enumerate(samples):
+        if b not in compressed:
+            h, w = data['image'].shape[:2]
+            offset[b] = pos
+            geom[b] = (3 * w, h, w) + _window_row(data)
+            pos += 3 * h * w
+    raw = np.empty(pos, np.uint8)
+    for b, data in enumerate(samples):
+        if b not in compressed:
+            raw[offset[b]:offset[b] + data['image'].size] = data['image'].reshape(-1)
+    extra = {}
+    if compressed:
+        # the decoded images live behind the host's pixels, on the device only: rows and images start where the decoder's 12-byte stores are aligned
+        for b in compressed:
+            h, w = samples[b]['image'].shape[:2]
+            stride = -(-3 * w // ROT_ROW_ALIGN) * ROT_ROW_ALIGN
+            pos = -(-pos // ROT_IMAGE_ALIGN) * ROT_IMAGE_ALIGN
+            offset[b] = pos
+            geom[b] = (stride, h, w) + _window_row(samples[b])
+            pos += h * stride
+        files = [samples[b]['image'] for b in compressed]
+        jpeg_offset = np.cumsum([0] + [f.data.size for f in files]).astype(np.int64)
+        desc = np.stack([f.desc for f in files])
+        need = int(_hip.lib().y2_jpeg_workspace_bytes(desc.ctypes.data, len(files)))
+        if need < 0:
+            raise ValueError('collate: a JpegImage carries a descriptor that y2_jpeg_probe_host did not fill')
+        extra.update(jpeg=torch.from_numpy(np.concatenate([f.data for f in files])), jpeg_offset=torch.from_numpy(jpeg_offset[:-1].copy()),
+                     jpeg_desc=torch.from_numpy(desc), jpeg_index=torch.from_numpy(np.array(compressed, np.int64)),
+                     jpeg_dst=torch.from_numpy(offset[compressed]), jpeg_geom=torch.from_numpy(geom[compressed]), jpeg_ws_bytes=need, raw_bytes=pos)
+    return raw, offset, geom, pos, extra
 
 
 class Collate(object):
@@ -278,39 +349,7 @@ class Collate(object):
                 self._keep(data)
                 raise
         out = {key: torch.from_numpy(np.stack([data[key] for data in samples])) for key in LABELS}      # (what default_collate makes of numpy arrays)
-        offset = np.zeros(len(samples), np.int64)
-        geom = np.zeros((len(samples), 8), np.int32)
-        pos = 0
-        compressed = [b for b, data in enumerate(samples) if isinstance(data['image'], JpegImage)]
-        for b, data in enumerate(samples):
-            if b not in compressed:
-                h, w = data['image'].shape[:2]
-                offset[b] = pos
-                geom[b] = (3 * w, h, w) + tuple(data['window']) + (int(bool(data['flip'])),)
-                pos += 3 * h * w
-        raw = np.empty(pos, np.uint8)
-        for b, data in enumerate(samples):
-            if b not in compressed:
-                raw[offset[b]:offset[b] + data['image'].size] = data['image'].reshape(-1)
-        extra = {}
-        if compressed:
-            # the decoded images live behind the host's pixels, on the device only: rows and images start where the decoder's 12-byte stores are aligned
-            for b in compressed:
-                h, w = samples[b]['image'].shape[:2]
-                stride = -(-3 * w // ROT_ROW_ALIGN) * ROT_ROW_ALIGN
-                pos = -(-pos // ROT_IMAGE_ALIGN) * ROT_IMAGE_ALIGN
-                offset[b] = pos
-                geom[b] = (stride, h, w) + tuple(samples[b]['window']) + (int(bool(samples[b]['flip'])),)
-                pos += h * stride
-            files = [samples[b]['image'] for b in compressed]
-            jpeg_offset = np.cumsum([0] + [f.data.size for f in files]).astype(np.int64)
-            desc = np.stack([f.desc for f in files])
-            need = int(_hip.lib().y2_jpeg_workspace_bytes(desc.ctypes.data, len(files)))
-            if need < 0:
-                raise ValueError('collate: a JpegImage carries a descriptor that y2_jpeg_probe_host did not fill')
-            extra.update(jpeg=torch.from_numpy(np.concatenate([f.data for f in files])), jpeg_offset=torch.from_numpy(jpeg_offset[:-1].copy()),
-                         jpeg_desc=torch.from_numpy(desc), jpeg_index=torch.from_numpy(np.array(compressed, np.int64)),
-                         jpeg_dst=torch.from_numpy(offset[compressed]), jpeg_geom=torch.from_numpy(geom[compressed]), jpeg_ws_bytes=need, raw_bytes=pos)
+        raw, offset, geom, pos, extra = pack_images(samples)
         if any('rotate' in data for data in samples):
             # every sample goes through the warp stage (an un-rotated one with the identity, an exact copy): what was packed above is its source, and
             # offset / geom move on to the rotated images inside the intermediate buffer
@@ -343,6 +382,37 @@ class Collate(object):
                    swap_rb=self.swap_rb, normalize=self.normalize)
         out.update(extra)
         return out
+
+
+def collate_images(samples, resize, height, width, swap_rb=True, normalize=(0.5, 1.0)):
+    """The label-less counterpart of Collate.__call__ (the test path: detect.Detector): `samples` are dicts whose `image` is a uint8 [h, w, 3] array or a
+    JpegImage, `resize` one of transform.resize.image (called as resize(data, height, width): it records, it does not resample).  Returns the batch
+    dict of to_device - `raw` / `offset` / `geom` and the JPEG tables packed by the code of Collate, `size`, `swap_rb`, `normalize` - and, when the
+    samples carry `fixed`, `fixed_geom` int32 [B, 4] {row_stride_bytes, src_h, src_w, mode} and `fixed_inv` float64 [B, 6], the inverse of each
+    recorded matrix (invert_affine): to_device then launches y2_fixed_images in place of y2_collate_images.  A batch that mixes `fixed` and windowed
+    samples raises."""
+    prepared = []
+    for data in samples:
+        data = resize(data, height, width)
+        image = data['image']
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError('collate_images: an image must be uint8 [h, w, 3] (got %s %s)' % (image.dtype, image.shape))
+        prepared.append(data)
+    fixed = ['fixed' in data for data in prepared]
+    if any(fixed) and (not all(fixed) or any('window' in data for data in prepared)):
+        raise ValueError('collate_images: the batch mixes `fixed` and windowed samples (one resize per batch)')
+    raw, offset, geom, pos, extra = pack_images(prepared)
+    check_geometry(offset, geom, pos)
+    out = dict(raw=torch.from_numpy(raw), offset=torch.from_numpy(offset), geom=torch.from_numpy(geom), size=(int(height), int(width)),
+               swap_rb=bool(swap_rb), normalize=None if normalize is None else (float(normalize[0]), float(normalize[1])))
+    out.update(extra)
+    if any(fixed):
+        fixed_geom = np.ascontiguousarray(geom[:, [0, 1, 2, 2]])
+        fixed_geom[:, 3] = [int(data['fixed']['mode']) for data in prepared]
+        fixed_inv = np.stack([invert_affine(data['fixed']['matrix']) for data in prepared]).reshape(-1, 6)
+        check_fixed(offset, fixed_geom, fixed_inv, pos)
+        out.update(fixed_geom=torch.from_numpy(fixed_geom), fixed_inv=torch.from_numpy(fixed_inv))
+    return out
 
 
 _LUT = {}
@@ -383,7 +453,11 @@ def to_device(batch, device=None, out=None, rot=None):
     that: the pixel buffer of `batch['raw_bytes']` bytes is allocated on `device`, the host-decoded pixels of `raw` are copied to its front, the files
     (`jpeg`, `jpeg_offset`, `jpeg_desc`) follow, and the decoder writes the JpegImage samples where `jpeg_dst` / `jpeg_geom` (their `offset` / `geom`
     rows before any rotation) say.  The result carries the buffer as `raw` and `jpeg_status` (int32, one per `jpeg_index` entry, 0 = decoded: the
-    status column of include/yolo2_hip.h) on `device`, un-synchronised: the caller decides when to look at it."""
+    status column of include/yolo2_hip.h) on `device`, un-synchronised: the caller decides when to look at it.
+    A batch with `fixed_geom` (collate_images with transform.resize.image.fixed: the test-time aspect-preserving resize) launches y2_fixed_images IN
+    PLACE of y2_collate_images ('cpu': y2_fixed_images_host), behind the JPEG decode when there is one: `fixed_geom` int32 [B, 4] and `fixed_inv`
+    float64 [B, 6] are checked while they are host memory (ValueError, nothing is written).  Such a batch with `warp` or `jitter` raises: the test
+    path has neither."""
     raw = batch['raw']
     if device is None:
         device = raw.device if raw.is_cuda else torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
@@ -393,6 +467,9 @@ def to_device(batch, device=None, out=None, rot=None):
     H, W = (int(v) for v in batch['size'])
     warped = 'warp' in batch
     compressed = 'jpeg' in batch
+    fixed = 'fixed_geom' in batch
+    if fixed and (warped or 'jitter' in batch):
+        raise ValueError('to_device: a batch with fixed_geom (the test-time `fixed` resize) cannot carry warp or jitter')
     source = int(batch['raw_bytes']) if compressed else raw.numel()      # the buffer of source pixels: `raw`, and behind it the images the device decodes
     pixels = int(batch['rot_bytes']) if warped else source               # the buffer that offset / geom index
     if not batch['geom'].is_cuda and not batch['offset'].is_cuda:
@@ -402,6 +479,9 @@ def to_device(batch, device=None, out=None, rot=None):
     jittered = 'jitter' in batch
     if jittered and not any(batch[k].is_cuda for k in ('jitter', 'hsv_tab', 'lut_b') if k in batch):
         check_jitter(batch['jitter'].numpy(), batch.get('hsv_tab'), batch['lut_b'], batch['geom'].size(0))
+    if fixed:
+        if not any(batch[k].is_cuda for k in ('offset', 'fixed_geom', 'fixed_inv')):
+            check_fixed(batch['offset'].numpy(), batch['fixed_geom'].numpy(), batch['fixed_inv'].numpy(), pixels)
     res = {k: (v.to(device, non_blocking=v.is_pinned()) if torch.is_tensor(v) and not (compressed and k == 'raw') else v) for k, v in batch.items()}
     jpeg_args = None
     if compressed:
@@ -423,7 +503,13 @@ def to_device(batch, device=None, out=None, rot=None):
     B = geom.size(0)
     if raw.dtype != torch.uint8 or offset.dtype != torch.int64 or geom.dtype != torch.int32 or geom.dim() != 2 or geom.size(1) != 8 or offset.numel() != B:
         raise ValueError('to_device: raw must be uint8, offset int64 [B], geom int32 [B, 8]')
-    if not (0 < W <= _hip.COLLATE_MAX_W and H > 0):
+    if fixed:
+        fixed_geom, fixed_inv = res['fixed_geom'].contiguous(), res['fixed_inv'].contiguous()
+        if fixed_geom.dtype != torch.int32 or fixed_inv.dtype != torch.float64 or tuple(fixed_geom.shape) != (B, 4) or tuple(fixed_inv.shape) != (B, 6):
+            raise ValueError('to_device: fixed_geom must be int32 [B, 4] and fixed_inv float64 [B, 6]')
+        if not (0 < W <= _hip.WARP_MAX_DIM and 0 < H <= _hip.WARP_MAX_DIM):
+            raise ValueError('to_device: size %dx%d (height and width are limited to %d)' % (H, W, _hip.WARP_MAX_DIM))
+    elif not (0 < W <= _hip.COLLATE_MAX_W and H > 0):
         raise ValueError('to_device: size %dx%d (the width is limited to %d)' % (H, W, _hip.COLLATE_MAX_W))
     raw, offset, geom = raw.contiguous(), offset.contiguous(), geom.contiguous()
     lut = res.get('lut')
@@ -458,8 +544,10 @@ def to_device(batch, device=None, out=None, rot=None):
                      B, max_h, max_w, int(batch.get('fill', 0)))
         raw = res['rot'] = rot
     tables = (jitter.data_ptr(), None if hsv_tab is None else hsv_tab.data_ptr(), lut.data_ptr()) if jittered else (lut.data_ptr(),)
-    args = (raw.data_ptr(), offset.data_ptr(), geom.data_ptr()) + tables + (B, H, W, 1 if batch.get('swap_rb', True) else 0, out.data_ptr())
-    name = 'y2_collate_jitter_images' if jittered else 'y2_collate_images'
+    if fixed:
+        tables = (fixed_geom.data_ptr(), fixed_inv.data_ptr(), lut.data_ptr())
+    args = (raw.data_ptr(), offset.data_ptr()) + (() if fixed else (geom.data_ptr(),)) + tables + (B, H, W, 1 if batch.get('swap_rb', True) else 0, out.data_ptr())
+    name = 'y2_fixed_images' if fixed else 'y2_collate_jitter_images' if jittered else 'y2_collate_images'
     if device.type == 'cuda':
         with torch.cuda.device(device):
             if compressed:
