@@ -751,8 +751,8 @@ int y2_region_loss_bwd(const float* iou, const float* center_offset, const float
 typedef struct {
     float* param;
     float* grad;
-    float* state1;   /* SGD: momentum buffer (NULL when momentum == 0); Adam: exp_avg */
-    float* state2;   /* Adam: exp_avg_sq; SGD: NULL */
+    float* state1;   /* SGD: momentum buffer (NULL when momentum == 0); Adam: exp_avg; RMSprop: square_avg */
+    float* state2;   /* Adam: exp_avg_sq; SGD: NULL; RMSprop: momentum buffer (NULL when momentum == 0) */
     int64_t numel;
 } y2_opt_tensor;
 
@@ -762,6 +762,19 @@ int y2_opt_sgd(const y2_opt_tensor* tensors, int32_t count, float lr, float mome
 /* torch.optim.Adam (no amsgrad), `step` = 1-based step count of these tensors (bias corrections computed in double on the host) */
 int y2_opt_adam(const y2_opt_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, float weight_decay,
                 int32_t step, y2_stream_t stream);
+/* torch.optim.RMSprop (its single-tensor formula, statement by statement, unfused):
+ *   d = g + weight_decay*p (when weight_decay != 0);  square_avg = square_avg*alpha + (1-alpha)*d*d;
+ *   centered: grad_avg += (1-alpha)*(d - grad_avg), avg = sqrt(square_avg - grad_avg^2);  otherwise avg = sqrt(square_avg);
+ *   avg += eps;  momentum != 0: buf = buf*momentum + d/avg, p -= lr*buf;  otherwise p -= lr*d/avg.
+ * state1 = square_avg (required), state2 = momentum_buffer (required iff momentum != 0, not read otherwise).  grad_avg: HOST array of `count`
+ * device pointers, required (every entry) iff centered, not read otherwise - centred RMSprop with momentum has three states, y2_opt_tensor two.
+ * Rounding: one fp32 rounding per operation, and ONE for each of g + weight_decay*p, square_avg*alpha [rounded] + (1-alpha)*(d*d [rounded]),
+ * grad_avg + (1-alpha)*(d - grad_avg [rounded]) and p - lr*x (fused multiply-adds, as torch's element-wise GPU kernels compute them).
+ * New states start as zeros (the caller's).  alpha is a double: 1 - alpha is formed in double and then rounded to fp32, as torch does with the Python float.  Same chunking and 16-B / scalar paths as the others
+ * (a tensor takes the 16-B path when param, grad and every state it uses are 16-B aligned); no allocation, no synchronisation, capturable.
+ * Y2_EINVAL (nothing launched): count outside 1..Y2_OPT_MAX_TENSORS, a NULL param / grad / required state, numel <= 0. */
+int y2_opt_rmsprop(const y2_opt_tensor* tensors, int32_t count, float* const* grad_avg, float lr, double alpha, float eps, float weight_decay,
+                   float momentum, int32_t centered, y2_stream_t stream);
 /* *sumsq (fp64, pre-zeroed, accumulated across calls) += sum of squares of all gradients; then y2_opt_clip_grads scales every
  * gradient by max_norm / (sqrt(*sumsq) + 1e-6) when that is < 1 (torch.nn.utils.clip_grad_norm_, L2).  No host sync. */
 int y2_opt_grad_sumsq(const y2_opt_tensor* tensors, int32_t count, double* sumsq, y2_stream_t stream);

@@ -86,6 +86,7 @@ SIGNATURES = {
     'y2_wino6_weight': [c_void_p, c_void_p, c_int, c_int, c_void_p],
     'y2_opt_sgd': [ctypes.POINTER(OptTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p],
     'y2_opt_adam': [ctypes.POINTER(OptTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p],
+    'y2_opt_rmsprop': [ctypes.POINTER(OptTensor), c_int, ctypes.POINTER(c_void_p), c_float, ctypes.c_double, c_float, c_float, c_float, c_int, c_void_p],
     'y2_opt_grad_sumsq': [ctypes.POINTER(OptTensor), c_int, c_void_p, c_void_p],
     'y2_opt_clip_grads': [ctypes.POINTER(OptTensor), c_int, c_void_p, c_float, c_void_p],
     'y2_wino_wgrad_workspace_bytes': [c_int, c_int, c_int, c_int, c_int],

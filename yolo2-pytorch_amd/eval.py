@@ -1,15 +1,29 @@
-"""`eval` — the matching and mAP arithmetic of the reference's VOC evaluation (eval.py:57-121, 140-162, 278-301).
+"""`eval` — the VOC evaluation of the reference (eval.py): the matching and mAP arithmetic, the `Eval` class and the command line.
 
 `matching` / `_matching` mirror the reference per (image, class) on the IoU kernel (y2_iou_rowmax).  `match_batch` is the batch form of the whole
 loop eval.py:278-292 - filter_valid, the per-class ground-truth counts, filter_cls_*, matching - as ONE launch (y2_eval_match; CPU tensors:
 y2_eval_match_host), and `Accumulator` carries its flags to `voc_ap` / `average_precision` / `merge_ap` (host numpy float64, like the reference)
-without host traffic per image or class.  The TinyDB / xlsx reporting, the data loader and the `Eval` class are out of scope."""
+without host traffic per image or class.
+
+`Eval(args, config)()` is the reference's class around them: the newest checkpoint of the model directory, the `[eval] phase` cache files through
+utils.data.Dataset / Collate (`[transform] resize_eval`, the single `[image] size`), and per batch utils.data.to_device -> the network ->
+detect.detect_batch / expand_batch -> Accumulator.update, with nothing crossing to the host until the end.  It returns {class index: AP}, logs
+`name=AP` and the mean, and appends one row to `[eval] db` as plain JSON in TinyDB's file layout, {"_default": {"1": row, "2": row, ...}}.
+`python eval.py -c config.ini [-m section/option=value ...] [-b 64] [--logging logging.yml]` is `main`.  Not here: the xlsx report (xlsxwriter)
+and the `[eval] mapper` file that names the reference's columns - the row has fixed keys instead (`save_db`)."""
+import argparse
 import configparser
+import datetime
+import json
+import logging
+import logging.config
+import os
 
 import numpy as np
 import torch
 
 import _hip
+import utils
 import utils.iou.torch
 
 
@@ -195,3 +209,126 @@ class Accumulator(object):
 
     def mean_ap(self, metric07=None):
         return float(np.mean(list(self.result(metric07).values())))
+
+
+def save_db(path, row):
+    """Append `row` (a JSON-serialisable dict) to the evaluation database `path`: {"_default": {"1": row, "2": row, ...}}, the file layout the
+    reference reads back with json.load(f)['_default'].  Returns the row's key."""
+    table = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            table = json.load(f).get('_default', {})
+    key = str(max([int(k) for k in table] + [0]) + 1)
+    table[key] = row
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + '.tmp'
+    with open(tmp, 'w') as f:
+        json.dump({'_default': table}, f)
+    os.replace(tmp, path)
+    return key
+
+
+class Eval(object):
+    """The reference's class of this name (eval.py:165-347) on the device-resident pieces.  args: `batch_size`; config: `[eval]`, `[detect]`,
+    `[image] size`, `[transform] resize_eval` / `image_test` / `tensor`, `[data] workers`.
+    detector (tests): an object called with the device batch (the dict of utils.data.to_device) in place of the network and the detection chain; it
+    returns a dict like detect.expand_batch's, with the boxes in cells of `grid=(rows, cols)` when it carries that key and as fractions of the image
+    otherwise.  With a detector no checkpoint is loaded onto a device (its step and epoch are still read for the database row)."""
+
+    def __init__(self, args, config, detector=None):
+        import model
+        import utils.train
+        self.args, self.config, self.detector = args, config, detector
+        self.model_dir = utils.get_model_dir(config)
+        self.cache_dir = utils.get_cache_dir(config)
+        self.category = utils.get_category(config, self.cache_dir)
+        self.anchors = torch.from_numpy(utils.get_anchors(config)).contiguous()
+        self.size = tuple(int(v) for v in config.get('image', 'size').split())
+        self.fix = config.getboolean('detect', 'fix')
+        self.kwargs = dict(fix=self.fix, threshold=config.getfloat('detect', 'threshold'), threshold_cls=config.getfloat('detect', 'threshold_cls'),
+                           overlap=config.getfloat('detect', 'overlap'))
+        self.loader = self.get_loader()
+        self.path, self.step, self.epoch = utils.train.load_model(self.model_dir)
+        if detector is None:
+            state_dict = torch.load(self.path, map_location='cpu')
+            dnn = utils.parse_attr(config.get('model', 'dnn'))(model.ConfigChannels(config, state_dict), self.anchors, len(self.category))
+            dnn.load_state_dict(state_dict)
+            self.dnn = dnn.eval().cuda()
+            self.anchors_device = self.anchors.to(next(self.dnn.parameters()).device, torch.float32).contiguous()
+        self.now = datetime.datetime.now()
+
+    def get_loader(self):
+        import detect
+        import utils.data
+        paths = [os.path.join(self.cache_dir, phase + '.pkl') for phase in self.config.get('eval', 'phase').split()]
+        dataset = utils.data.Dataset(utils.data.load_pickles(paths))
+        logging.info('num_examples=%d' % len(dataset))
+        try:
+            workers = self.config.getint('data', 'workers')
+        except (configparser.NoSectionError, configparser.NoOptionError):
+            workers = min(os.cpu_count() or 1, 16)
+        swap_rb, normalize = detect.image_options(self.config)
+        collate_fn = utils.data.Collate(detect.parse_resize(self.config, self.config.get('transform', 'resize_eval')), [self.size], swap_rb=swap_rb, normalize=normalize)
+        return torch.utils.data.DataLoader(dataset, batch_size=self.args.batch_size, num_workers=workers, collate_fn=collate_fn, pin_memory=torch.cuda.is_available())
+
+    def detect(self, data):
+        """(detections, grid) of one device batch: the sequence tools/eval_bench.py times."""
+        import detect
+        if self.detector is not None:
+            dets = self.detector(data)
+            return dets, dets.get('grid')
+        with torch.no_grad():
+            feature = self.dnn.forward_nhwc(data['tensor'])
+            d = detect.detect_batch(feature, self.anchors_device, **self.kwargs)
+            return detect.expand_batch(d, self.fix, self.kwargs['threshold_cls']), tuple(feature.shape[1:3])
+
+    def stat_ap(self):
+        import utils.data
+        acc = Accumulator(self.config, num_cls=len(self.category))
+        for batch in self.loader:
+            data = utils.data.to_device(batch)
+            dets, grid = self.detect(data)
+            acc.update(data, dets, image_size=self.size, grid=grid)
+        return acc
+
+    def logging(self, cls_ap):
+        for c in cls_ap:
+            logging.info('%s=%f' % (self.category[c], cls_ap[c]))
+        logging.info(np.mean(list(cls_ap.values())) if cls_ap else 'no class with ground truth')
+
+    def row(self, cls_ap):
+        return dict(timestamp=self.now.timestamp(), time=self.now.isoformat(), step=self.step, epoch=self.epoch, dnn=self.config.get('model', 'dnn'),
+                    size='%d %d' % self.size, mean_ap=float(np.mean(list(cls_ap.values()))) if cls_ap else None,
+                    cls_ap={self.category[c]: float(ap) for c, ap in cls_ap.items()})
+
+    def __call__(self):
+        cls_ap = self.stat_ap().result()
+        save_db(utils.get_eval_db(self.config), self.row(cls_ap))
+        self.logging(cls_ap)
+        return cls_ap
+
+
+def main(argv=None, detector=None):
+    args = make_args(argv)
+    config = configparser.ConfigParser()
+    utils.load_config(config, args.config)
+    for cmd in args.modify:
+        utils.modify_config(config, cmd)
+    if args.logging:
+        import yaml
+        with open(os.path.expanduser(os.path.expandvars(args.logging)), 'r') as f:
+            logging.config.dictConfig(yaml.safe_load(f))
+    return Eval(args, config, detector)()
+
+
+def make_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('-c', '--config', nargs='+', default=['config.ini'], help='config file')
+    parser.add_argument('-m', '--modify', nargs='+', default=[], help='modify config')
+    parser.add_argument('-b', '--batch_size', default=16, type=int, help='batch size')
+    parser.add_argument('--logging', default=None, help='logging config (yaml), optional')
+    return parser.parse_args(argv)
+
+
+if __name__ == '__main__':
+    main()

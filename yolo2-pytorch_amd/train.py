@@ -10,19 +10,41 @@ nn.DataParallel) and rank 0's running statistics are the ones a checkpoint sees.
 output gather.  The cls term's mean over positives uses the GLOBAL positive count (one scalar all-reduce) so that the
 averaged gradient equals the single-process gradient on the concatenated batch.
 
-Only the hot-path pieces of train.py are mirrored (`norm_data` :57-62, `ensure_model` :65-71, the body of
-`Train.iterate` :338-362 as `iterate`); the dataset / TensorBoard / checkpoint harness is out of scope.
+`norm_data` (:57-62), `ensure_model` (:65-71) and `iterate` (the body of `Train.iterate`, :338-362) are the hot path.  `Train(args, config)()` is the
+reference's class around them and `python train.py -c config.ini -b 64` its command line (`main`, `make_args`: the reference's flags): checkpoints
+through utils.train.Saver, resume and `--finetune`, the optimizer and the scheduler from their ini lambdas, utils.data.Dataset / Collate with the
+`[transform]` plugins, utils.data.to_device + `iterate` per step, `check_nan` before every save, the best model by mAP beside the model directory.
+Where it deviates from the reference (all stated in README.md): evaluation runs on the checkpoint just saved with the training model left on the GPU;
+scalar summaries go to <model_dir>/<run>/scalars.jsonl (no tensorboardX; no image or histogram summaries, no SummaryWorker process); `<step>.epoch`
+holds the last COMPLETED epoch and a resumed run starts with the one after it; WORLD_SIZE > 1 raises (`iterate` under DataParallelRCCL is the
+multi-GPU interface).
 """
+import argparse
+import collections
+import configparser
+import hashlib
+import io
+import json
 import logging
+import logging.config
 import os
+import pickle
+import shutil
+import subprocess
+import sys
+import warnings
 
 import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
+import torch.optim
+import torch.utils.data
 
 import model
 import utils
+import utils.train
+import eval as _eval          # (under another name: the ini lambdas below are evaluated with the builtin)
 
 BUCKET_BYTES = 25 * 1024 * 1024
 
@@ -716,3 +738,312 @@ def iterate(inference, optimizer, data, loss_hparam, threshold, anchors, clip=No
         utils.optim.clip_grad_norm_(inference.parameters(), clip)     # fused form of nn.utils.clip_grad_norm (train.py:352-354)
     optimizer.step()
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the Train class and the command line
+LOSS_KEYS = ('foreground', 'background', 'center', 'size', 'cls')
+
+
+def load_hparam(config):
+    """`[hparam]`: the weight of every loss term."""
+    return {key: config.getfloat('hparam', key) for key in LOSS_KEYS if config.has_option('hparam', key)}
+
+
+def make_optimizer(config, parameters, lr):
+    """`[train] optimizer = lambda params, lr: ...` over the parameters that require a gradient."""
+    return eval(config.get('train', 'optimizer'))([p for p in parameters if p.requires_grad], lr)
+
+
+def make_scheduler(config, optimizer):
+    """`[train] scheduler = lambda optimizer: ...`, or None without the option."""
+    if not config.has_option('train', 'scheduler'):
+        return None
+    return eval(config.get('train', 'scheduler'))(optimizer)
+
+
+def set_epoch(scheduler, epoch):
+    """The learning rates of epoch `epoch`, what the reference's `scheduler.step(epoch)` sets: the scheduler is stepped until its count is
+    `epoch` (a fresh one counts 0), so a run resumed in epoch e starts with the rate of epoch e.  Returns the rates."""
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', UserWarning)          # (torch warns when a scheduler steps before the optimizer did: a resumed run does exactly that)
+        while scheduler.last_epoch < epoch:
+            scheduler.step()
+    return [group['lr'] for group in scheduler.optimizer.param_groups]
+
+
+def finetune(dnn, path, ignore=()):
+    """Copy every tensor of the checkpoint `path` (a file, or a model directory: its newest checkpoint) into `dnn`, except the keys a pattern of
+    `ignore` matches (utils.RegexList: at the start of the key); a key of `dnn` the file lacks is reported and stays."""
+    if os.path.isdir(path):
+        path, _, _ = utils.train.load_model(path)
+    loaded = torch.load(path, map_location='cpu')
+    state_dict = dnn.state_dict()
+    skip = utils.RegexList(ignore)
+    for key in state_dict:
+        if skip(key):
+            continue
+        if key in loaded:
+            state_dict[key] = loaded[key]
+        else:
+            logging.warning('%s not in finetune file %s' % (key, path))
+    dnn.load_state_dict(state_dict)
+    return path
+
+
+def check_nan(model_dir, dnn, step, loss_total, loss, data):
+    """A NaN total: the weights (`model.pth`) and the batch (`data.pth`) go to <model_dir>/<step>/ and OverflowError is raised."""
+    if not np.isnan(float(loss_total)):
+        return
+    dump_dir = os.path.join(model_dir, str(step))
+    os.makedirs(dump_dir, exist_ok=True)
+    torch.save(collections.OrderedDict((key, var.cpu()) for key, var in dnn.state_dict().items()), os.path.join(dump_dir, 'model.pth'))
+    torch.save({key: (var.cpu() if torch.is_tensor(var) else var) for key, var in data.items()}, os.path.join(dump_dir, 'data.pth'))
+    for key, value in loss.items():
+        logging.warning('%s=%f' % (key, float(value)))
+    raise OverflowError('NaN loss detected, dump runtime information into ' + dump_dir)
+
+
+def make_augmentation(config):
+    """`[transform] augmentation`: the plugins (transform.augmentation.RandomRotate ...), each built with the config, applied in order."""
+    plugins = [utils.parse_attr(name)(config) for name in config.get('transform', 'augmentation', fallback='').split()]
+
+    def transform(data):
+        for plugin in plugins:
+            data = plugin(data)
+        return data
+    return transform
+
+
+def make_loader(config, cache_dir, model_dir, num_cls, batch_size):
+    """The training DataLoader (train.py:285-309): the `[train] phase` cache files through utils.data.Dataset (augmentation on the labels) and
+    utils.data.Collate (`resize_train`, a size of `[data] sizes` per `maintain` batches, `image_train`); `[data] workers` processes.  What it yields
+    goes to utils.data.to_device."""
+    import detect
+    import transform.image
+    import utils.data
+    paths = [os.path.join(cache_dir, phase + '.pkl') for phase in config.get('train', 'phase').split()]
+    keep = os.path.join(model_dir, 'exception')
+    dataset = utils.data.Dataset(utils.data.load_pickles(paths), transform=make_augmentation(config),
+                                 one_hot=None if config.getboolean('train', 'cross_entropy') else num_cls,
+                                 shuffle=config.getboolean('data', 'shuffle', fallback=False), dir=keep)
+    logging.info('num_examples=%d' % len(dataset))
+    try:
+        workers = config.getint('data', 'workers')
+    except (configparser.NoSectionError, configparser.NoOptionError):
+        workers = min(os.cpu_count() or 1, 16)
+    normalize = None
+    for name in config.get('transform', 'tensor', fallback='torchvision.transforms.ToTensor transform.image.Normalize').split():
+        if name == 'transform.image.Normalize':
+            plugin = transform.image.Normalize(config)
+            normalize = (plugin.mean, plugin.std)
+        elif name != 'torchvision.transforms.ToTensor':
+            raise ValueError('[transform] tensor: %s is not served by the level table (ToTensor and transform.image.Normalize are)' % name)
+    collate_fn = utils.data.Collate(detect.parse_resize(config, config.get('transform', 'resize_train')), utils.train.load_sizes(config),
+                                    maintain=config.getint('data', 'maintain', fallback=1), normalize=normalize, dir=keep,
+                                    transform_image=transform.image.get_transform(config, config.get('transform', 'image_train', fallback='transform.image.BGR2RGB').split()))
+    return torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=True, num_workers=workers, collate_fn=collate_fn, pin_memory=torch.cuda.is_available())
+
+
+class Train(object):
+    """The reference's class of this name (train.py:244-447).  args: make_args(); config: the ini.  Train(args, config)() trains until `args.epoch`."""
+
+    def __init__(self, args, config):
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise NotImplementedError('train.Train: WORLD_SIZE > 1 is not served by the command line (one process, one GPU); multi-GPU steps are '
+                                      'train.iterate under train.DataParallelRCCL, from Python')
+        self.args, self.config = args, config
+        self.model_dir = utils.get_model_dir(config)
+        self.cache_dir = utils.get_cache_dir(config)
+        self.category = utils.get_category(config, self.cache_dir)
+        self.anchors = torch.from_numpy(utils.get_anchors(config)).contiguous()
+        logging.info('use cache directory ' + self.cache_dir)
+        if args.delete:
+            logging.warning('delete model directory: ' + self.model_dir)
+            shutil.rmtree(self.model_dir, ignore_errors=True)
+        os.makedirs(self.model_dir, exist_ok=True)
+        with open(self.model_dir + '.ini', 'w') as f:
+            config.write(f)
+        self.step, self.epoch, self.dnn = self.load()
+        self.inference = model.Inference(config, self.dnn, self.anchors)
+        if args.finetune:
+            path = os.path.expanduser(os.path.expandvars(args.finetune))
+            logging.info('finetune from ' + path)
+            finetune(self.dnn, path, args.ignore)
+        self.inference = ensure_model(self.inference)
+        self.inference.train()
+        self.optimizer = make_optimizer(config, self.inference.parameters(), args.learning_rate)
+        self.hparam = load_hparam(config)
+        self.threshold = config.getfloat('model', 'threshold')
+        self.clip = config.getfloat('train', 'clip') if config.has_option('train', 'clip') else None
+        self.saver = utils.train.Saver(self.model_dir, config.getint('save', 'keep'))
+        self.timer_save = utils.train.Timer(config.getfloat('save', 'secs'), False)
+        if config.has_option('eval', 'secs'):
+            self.timer_eval = utils.train.Timer(eval(config.get('eval', 'secs')), config.getboolean('eval', 'first', fallback=False))
+        else:
+            self.timer_eval = lambda: False
+        if config.has_option('summary', 'scalar'):
+            self.timer_scalar = utils.train.Timer(config.getfloat('summary', 'scalar'))
+        else:
+            self.timer_scalar = lambda: False
+        self.scalars = os.path.join(self.model_dir, str(args.run), 'scalars.jsonl')
+
+    def load(self):
+        """(step, completed epochs' last index or None, plugin): the newest checkpoint, or a fresh plugin at step 0."""
+        try:
+            path, step, epoch = utils.train.load_model(self.model_dir)
+            state_dict = torch.load(path, map_location='cpu')
+            config_channels = model.ConfigChannels(self.config, state_dict)
+        except (FileNotFoundError, ValueError):
+            step, epoch = 0, None
+            config_channels = model.ConfigChannels(self.config)
+        dnn = utils.parse_attr(self.config.get('model', 'dnn'))(config_channels, self.anchors, len(self.category))
+        if config_channels.state_dict is not None:
+            dnn.load_state_dict(config_channels.state_dict)
+        return step, epoch, dnn
+
+    def get_loader(self):
+        return make_loader(self.config, self.cache_dir, self.model_dir, len(self.category), self.args.batch_size)
+
+    def reserve(self):
+        """The activation arena of the training steps, sized for the largest of `[data] sizes` before the first step (shapes only: nothing runs)."""
+        params = [p for p in self.inference.parameters()]
+        if not params or not params[0].is_cuda:
+            return None
+        dev = params[0].device
+        height, width = max(utils.train.load_sizes(self.config), key=lambda size: size[0] * size[1])
+        B = self.args.batch_size
+        cls = torch.zeros(B, 1, dtype=torch.int64, device=dev) if self.config.getboolean('train', 'cross_entropy') else torch.zeros(B, 1, len(self.category), device=dev)
+        data = dict(tensor=torch.zeros(B, 3, height, width, device=dev), yx_min=torch.zeros(B, 1, 2, device=dev), yx_max=torch.zeros(B, 1, 2, device=dev), cls=cls)
+        return reserve(self.inference, data, self.hparam, self.threshold, self.anchors)
+
+    def iterate(self, batch):
+        import utils.data
+        data = utils.data.to_device(batch)
+        out = iterate(self.inference, self.optimizer, data, self.hparam, self.threshold, self.anchors, self.clip)
+        out['data'] = data
+        return out
+
+    def summary_scalar(self, step, epoch, loss, loss_total, **_):
+        """One line of <model_dir>/<run>/scalars.jsonl: the five loss terms, their weighted values and the total (one host synchronisation)."""
+        terms = {key: float(value) for key, value in loss.items()}
+        row = dict(step=step, epoch=epoch, loss=terms, loss_hparam={key: value * self.hparam[key] for key, value in terms.items()}, loss_total=float(loss_total))
+        os.makedirs(os.path.dirname(self.scalars), exist_ok=True)
+        with open(self.scalars, 'a') as f:
+            f.write(json.dumps(row) + '\n')
+
+    def save(self, step, epoch, loss, loss_total, data, completed=False, **_):
+        """check_nan, then <step>.pth with the tensors on the CPU.  <step>.epoch holds the last COMPLETED epoch: a save in the middle of epoch e
+        records e - 1 (none in epoch 0), so that the resumed run does epoch e again."""
+        check_nan(self.model_dir, self.dnn, step, loss_total, loss, data)
+        done = epoch if completed else (epoch - 1 if epoch > 0 else None)
+        return self.saver(collections.OrderedDict((key, var.cpu()) for key, var in self.dnn.state_dict().items()), step, done)
+
+    def eval(self, **kwargs):
+        """Save, then evaluate that checkpoint with eval.Eval (a second copy of the plugin in eval mode; the training model stays where it is), and
+        keep the best model.  A failing evaluation is logged and training goes on, as in the reference."""
+        logging.info('evaluating')
+        self.save(**kwargs)
+        try:
+            e = _eval.Eval(self.args, self.config)
+            cls_ap = e()
+            self.backup_best(cls_ap, e.path)
+        except Exception:
+            logging.exception('evaluation failed')
+
+    def backup_best(self, cls_ap, path):
+        """<model_dir>.pkl (the {class: AP} dict) and <model_dir>.pth (a copy of the checkpoint) of the best mean AP so far."""
+        try:
+            with open(self.model_dir + '.pkl', 'rb') as f:
+                best = np.mean(list(pickle.load(f).values()))
+        except (OSError, pickle.UnpicklingError, EOFError):
+            best = np.finfo(np.float32).min
+        metric = np.mean(list(cls_ap.values())) if cls_ap else np.finfo(np.float32).min
+        if metric > best or not os.path.exists(self.model_dir + '.pth'):
+            with open(self.model_dir + '.pkl', 'wb') as f:
+                pickle.dump(cls_ap, f)
+            shutil.copy(path, self.model_dir + '.pth')
+            logging.info('best model (%f) saved into %s.*' % (metric, self.model_dir))
+        else:
+            logging.info('best metric %f >= %f' % (best, metric))
+
+    def __call__(self):
+        import filelock
+        kwargs, batch = None, None
+        with filelock.FileLock(os.path.join(self.model_dir, 'lock'), 0):
+            try:
+                scheduler = make_scheduler(self.config, self.optimizer)
+                loader = self.get_loader()
+                logging.info('num_workers=%d' % loader.num_workers)
+                self.reserve()
+                step = self.step
+                first = 0 if self.epoch is None else self.epoch + 1
+                for epoch in range(first, self.args.epoch):
+                    if scheduler is not None:
+                        logging.info('epoch=%d, lr=%s' % (epoch, str(set_epoch(scheduler, epoch))))
+                    batches = loader
+                    if not self.args.quiet:
+                        import tqdm
+                        batches = tqdm.tqdm(loader, desc='epoch=%d/%d' % (epoch, self.args.epoch))
+                    for batch in batches:
+                        kwargs = self.iterate(batch)
+                        step += 1
+                        kwargs.update(step=step, epoch=epoch, completed=False)
+                        if self.timer_scalar():
+                            self.summary_scalar(**kwargs)
+                        if self.timer_eval():
+                            self.eval(**kwargs)
+                        elif self.timer_save():
+                            self.save(**kwargs)
+                    if kwargs is not None:
+                        kwargs.update(epoch=epoch, completed=True)          # (what a save records from here until the next step)
+                if kwargs is not None:
+                    self.save(**kwargs)
+                logging.info('finished')
+            except KeyboardInterrupt:
+                logging.warning('interrupted')
+                if kwargs is not None:
+                    self.save(**kwargs)
+            except Exception:
+                if batch is not None:
+                    with open(os.path.join(self.model_dir, 'data.pkl'), 'wb') as f:
+                        pickle.dump(batch, f)
+                raise
+        return step
+
+
+def main(argv=None):
+    args = make_args(argv)
+    config = configparser.ConfigParser()
+    utils.load_config(config, args.config)
+    for cmd in args.modify:
+        utils.modify_config(config, cmd)
+    if args.logging:
+        import yaml
+        with open(os.path.expanduser(os.path.expandvars(args.logging)), 'r') as f:
+            logging.config.dictConfig(yaml.safe_load(f))
+    if args.run is None:
+        buffer = io.StringIO()
+        config.write(buffer)
+        args.run = hashlib.md5(buffer.getvalue().encode()).hexdigest()
+    logging.info('cd ' + os.getcwd() + ' && ' + subprocess.list2cmdline([sys.executable] + sys.argv))
+    return Train(args, config)()
+
+
+def make_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('-c', '--config', nargs='+', default=['config.ini'], help='config file')
+    parser.add_argument('-m', '--modify', nargs='+', default=[], help='modify config')
+    parser.add_argument('-b', '--batch_size', default=16, type=int, help='batch size')
+    parser.add_argument('-f', '--finetune', help='a checkpoint file or a model directory to take the weights from')
+    parser.add_argument('-i', '--ignore', nargs='+', default=[], help='regex to ignore weights while finetuning')
+    parser.add_argument('-lr', '--learning_rate', default=1e-3, type=float, help='learning rate')
+    parser.add_argument('-e', '--epoch', type=int, default=np.iinfo(np.int64).max, help='train until this epoch')
+    parser.add_argument('-d', '--delete', action='store_true', help='delete model')
+    parser.add_argument('-q', '--quiet', action='store_true', help='quiet mode')
+    parser.add_argument('-r', '--run', help='the name of the run: scalars go to <model_dir>/<run>/scalars.jsonl')
+    parser.add_argument('--logging', default=None, help='logging config (yaml), optional')
+    return parser.parse_args(argv)
+
+
+if __name__ == '__main__':
+    main()

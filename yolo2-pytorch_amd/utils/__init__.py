@@ -6,6 +6,7 @@ model.yolo2.Darknet` (or `model.resnet.resnet50`, `model.yolo2.Tiny`) to the HIP
 import configparser
 import importlib
 import os
+import re
 
 import numpy as np
 import torch
@@ -17,6 +18,17 @@ def _path(p):
 
 def _root(config):
     return _path(config.get('config', 'root'))
+
+
+class RegexList(list):
+    """A list of compiled patterns; called with a string: does any of them match at its start?  (`--ignore` of train.py; the reference's class of
+    this name, utils/__init__.py:40-50.)"""
+
+    def __init__(self, patterns):
+        list.__init__(self, (re.compile(pattern) for pattern in patterns))
+
+    def __call__(self, text):
+        return any(pattern.match(text) is not None for pattern in self)
 
 
 def get_cache_dir(config):
