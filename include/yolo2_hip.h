@@ -232,7 +232,9 @@ int y2_conv0_fwd(const float* x_nchw, const float* w, const float* scale, const 
                  int B, int H, int W, int Cin, int Cout, int ldy, int ldp, float slope, y2_stream_t stream);
 /* The training forward of the first layer as a producer of z_sel (see y2_bn_act_fwd_sel): raw z (pixel stride ldz), its statistics, and z_sel
  * [B,H/2,W/2,Cout] (pixel stride ldzs) = per window the first z_q in scan order that maximises sign(gamma[c]) * z_q (strict comparison; gamma = the
- * BatchNorm weight, known before the batch statistics are).  z and stats are those of y2_conv0_fwd(x, w, NULL, NULL, z, NULL, stats, ..., 1.0). */
+ * BatchNorm weight, known before the batch statistics are).  z and stats are those of y2_conv0_fwd(x, w, NULL, NULL, z, NULL, stats, ..., 1.0).
+ * gamma, z and z_sel are required (NULL: Y2_EINVAL); stats may be NULL (deterministic mode, where statistics are refused, passes NULL): z and z_sel
+ * are then written all the same, for every Cin, Cout and row stride the plain entry accepts. */
 int y2_conv0_fwd_sel(const float* x_nchw, const float* w, const float* gamma, float* z, float* z_sel, double* stats,
                      int B, int H, int W, int Cin, int Cout, int ldz, int ldzs, y2_stream_t stream);
 

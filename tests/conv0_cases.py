@@ -2,9 +2,12 @@
 reach what they claim), and the Python mirror of the host code of csrc/conv0_fwd.hip:
 
     y2_conv0_fwd        the refusals with their codes, in the entry point's order; tiles_y, tiles_x, ntiles
+    y2_conv0_fwd_sel    its own refusal (gamma, z or z_sel NULL), then the shared body with no affine, slope 1 and pool_sign = gamma
     launch0             the persistent grid (Y2_NUM_CU * 8 workgroups or one per tile), how many tiles the busiest and the idlest workgroup walk, the
                         FULL condition, which of the eight straight-line (NBLK, OUT, RAW) variants a call gets or the general kernel with NBLK 1 / 2 -
-                        a pooled-only call whose slope lies outside [0, 1] falls through to the general kernel
+                        a pooled-only call whose slope lies outside [0, 1] falls through to the general kernel; a call with pool_sign gets the ninth
+                        straight-line variant (1, 7, RAW, launched outside the Y2_C0 list) when it asks for z, z_sel and statistics at Cout 32, and the
+                        general kernel - the only other code that selects - in every other case
 
 No torch and no library: plain integer arithmetic in the host code's order.
 
@@ -24,14 +27,26 @@ MASKS = {1: 'y', 2: 'p', 3: 'yp', 4: 's', 5: 'ys', 6: 'ps', 7: 'yps'}
 # (Cout / 32, out mask, RAW) of the straight-line instantiations launch0 has
 VARIANTS = ((1, 2, False), (1, 5, True), (1, 5, False), (1, 1, False), (1, 3, False), (2, 2, False), (2, 5, True), (2, 1, False))
 
-_C = collections.namedtuple('C', 'B cin cout H W outs scale shift slope ypad yoff ppad poff det nox now')
+SEL_VARIANT = (1, 7, True)      # ... and the one launched outside the Y2_C0 list: y2_conv0_fwd_sel's z + z_sel + statistics
+
+_C = collections.namedtuple('C', 'B cin cout H W outs scale shift slope ypad yoff ppad poff det nox now sel nog')
 
 
-def C(B, cin, cout, H, W, outs='y', scale=True, shift=True, slope=0.1, ypad=0, yoff=0, ppad=0, poff=0, det=False, nox=False, now=False):
-    """A y2_conv0_fwd call.  outs: the destinations given, a subset of 'y' (full), 'p' (2x2-pooled), 's' (statistics).  y has rows of ldy = cout + ypad
+def C(B, cin, cout, H, W, outs='y', scale=True, shift=True, slope=0.1, ypad=0, yoff=0, ppad=0, poff=0, det=False, nox=False, now=False, sel=False, nog=False):
+    """A y2_conv0_fwd call, or (sel or nog: see S) a y2_conv0_fwd_sel call.  outs: the destinations given, a subset of 'y' (full), 'p' (2x2-pooled), 's' (statistics).  y has rows of ldy = cout + ypad
     floats and is passed as y + yoff (ppad / poff: the same for y_pool; a negative pad is an ld below Cout).  det: deterministic mode is on.
     nox / now: x / w is NULL."""
-    return _C(B, cin, cout, H, W, outs, scale, shift, slope, ypad, yoff, ppad, poff, det, nox, now)
+    return _C(B, cin, cout, H, W, outs, scale, shift, slope, ypad, yoff, ppad, poff, det, nox, now, sel, nog)
+
+
+def S(B, cin, cout, H, W, outs='yps', nog=False, **kw):
+    """A y2_conv0_fwd_sel call: 'y' is z (rows of ldz = cout + ypad floats, passed as z + yoff), 'p' is z_sel (ldzs = cout + ppad, z_sel + poff), 's' the
+    statistics.  sel: gamma is given (nog: the entry is called with gamma NULL).  The entry passes no affine and slope 1 on."""
+    return C(B, cin, cout, H, W, outs, scale=False, shift=False, slope=1.0, sel=not nog, nog=nog, **kw)
+
+
+def is_sel_entry(c):
+    return c.sel or c.nog
 
 
 def cdiv(a, b):
@@ -42,7 +57,7 @@ def out_mask(outs):
     return ('y' in outs) * 1 + ('p' in outs) * 2 + ('s' in outs) * 4
 
 
-Route = collections.namedtuple('Route', 'rc kernel nblk out raw full tiles_y tiles_x ntiles grid walk_max walk_min')
+Route = collections.namedtuple('Route', 'rc kernel nblk out raw full tiles_y tiles_x ntiles grid walk_max walk_min sel', defaults=(False,))
 
 
 def _refuse(rc):
@@ -50,7 +65,11 @@ def _refuse(rc):
 
 
 def route(c):
-    """What y2_conv0_fwd and launch0 do with call c."""
+    """What y2_conv0_fwd (y2_conv0_fwd_sel for a call made by S) and launch0 do with call c."""
+    if is_sel_entry(c):
+        assert not c.scale and not c.shift and c.slope == 1.0, 'y2_conv0_fwd_sel has no affine to pass'
+        if c.nog or 'y' not in c.outs or 'p' not in c.outs:
+            return _refuse(EINVAL)
     if c.nox or c.now or not c.outs:
         return _refuse(EINVAL)
     if c.B <= 0 or c.H <= 0 or c.W <= 0 or c.cin < 1 or c.cin > 4 or c.cout < 1 or c.cout > 64:
@@ -74,7 +93,11 @@ def route(c):
         raw = not c.scale and not c.shift and c.slope == 1.0
         mono = 0.0 <= c.slope <= 1.0
         nb = c.cout // 32
-        if out == 2 and mono:
+        if c.sel and (nb, out, raw) == SEL_VARIANT:
+            return Route(OK, 'straight', nb, out, raw, True, ty, tx, tiles, grid, walk[0], walk[1], True)
+        if c.sel:
+            v = None                                # no instantiation of the Y2_C0 list selects: the general kernel
+        elif out == 2 and mono:
             v = (nb, 2, False)
         elif out == 5 and raw:
             v = (nb, 5, True)
@@ -86,11 +109,11 @@ def route(c):
             v = None
         if v is not None:
             return Route(OK, 'straight', v[0], v[1], v[2], True, ty, tx, tiles, grid, walk[0], walk[1])
-    return Route(OK, 'general', 1 if c.cout <= 32 else 2, out, False, False, ty, tx, tiles, grid, walk[0], walk[1])
+    return Route(OK, 'general', 1 if c.cout <= 32 else 2, out, False, False, ty, tx, tiles, grid, walk[0], walk[1], c.sel)
 
 
 def variant_name(r):
-    return 'sl%d-o%d%s' % (r.nblk, r.out, '-raw' if r.raw else '') if r.kernel == 'straight' else 'gen%d' % r.nblk
+    return ('sl%d-o%d%s' % (r.nblk, r.out, '-raw' if r.raw else '') if r.kernel == 'straight' else 'gen%d' % r.nblk) + ('-sel' if r.sel else '')
 
 
 def looks_aligned(c):
@@ -104,6 +127,8 @@ def claims_of(c):
     if r.rc != OK:
         return {'refused'}
     out = {variant_name(r), r.kernel, 'cin%d' % c.cin, 'nblk%d' % r.nblk, 'out%d' % out_mask(c.outs)}
+    if r.sel:
+        out.add('sel')
     out.add('walk%d' % r.walk_max if r.walk_max <= 4 else 'walk7+' if r.walk_max >= 7 else 'walk5-6')
     if r.walk_min == r.walk_max - 1:
         out.add('uneven-walk')
@@ -301,3 +326,68 @@ def first_refusing_test(c):
              's' in c.outs and c.det,
              c.B * cdiv(max(c.H, 0), TH) * cdiv(max(c.W, 0), TW) > 0x7fffffff)
     return [i for i, t in enumerate(tests) if t][0]
+
+
+# ================================================================================================ y2_conv0_fwd_sel
+# ---- every path a call with gamma can take: the ninth straight-line variant, and the general kernel wherever that variant does not apply
+SEL_SMALL = (2, 18, 34)          # (B, H, W) of the general kernel's mask and tap cases: the size of MASK_CASES and TAP_CASES
+SEL_CASES = collections.OrderedDict()
+for _s in ('small', 'walk3'):    # walk3: the first aligned size with tiles from the in-loop staging (290 MB of z)
+    _B, _H, _W = ALIGNED_SIZES[_s][0]
+    SEL_CASES['sel-sl-%s' % _s] = Case(S(_B, 3, 32, _H, _W), ALIGNED_SIZES[_s][1] | {'sl1-o7-raw-sel', 'straight', 'sel', 'out7'})
+# the call of a deterministic-mode user: no statistics, everything else as the shipped first layer has it.  launch0 once sent it to <3, 1, 3, true, false>,
+# which ignores pool_sign and writes the window maximum for every channel
+SEL_CASES['sel-nostats-aligned'] = Case(S(1, 3, 32, 16, 32, 'yp'), {'gen1-sel', 'fallthrough', 'out3', 'whole-tile', 'one-tile-image'})
+SEL_CASES['sel-nostats-ragged'] = Case(S(2, 3, 20, 18, 34, 'yp'), {'gen1-sel', 'out3', 'ragged-both'})
+SEL_CASES['sel-fall-cout64'] = Case(S(2, 3, 64, 32, 64), {'gen2-sel', 'fallthrough', 'out7'})
+SEL_CASES['sel-fall-cout64-nostats'] = Case(S(2, 3, 64, 32, 64, 'yp'), {'gen2-sel', 'fallthrough', 'out3'})
+SEL_CASES['sel-fall-ldz'] = Case(S(2, 3, 32, 32, 64, ypad=4), {'gen1-sel', 'fallthrough', 'out7', 'ld>cout'})
+SEL_CASES['sel-fall-ldzs'] = Case(S(2, 3, 32, 32, 64, ppad=4), {'gen1-sel', 'fallthrough', 'out7', 'ld>cout'})
+SEL_CASES['sel-fall-cin4'] = Case(S(2, 4, 32, 32, 64), {'gen1-sel', 'cin4', 'out7', 'whole-tile'})          # (not `looks aligned`, as FALL_CASES' fall-cin4)
+for _cout in MASK_COUTS:
+    SEL_CASES['sel-mask-cout%d' % _cout] = Case(S(SEL_SMALL[0], 3, _cout, SEL_SMALL[1], SEL_SMALL[2]),
+                                                 {'gen%d-sel' % (1 if _cout <= 32 else 2), 'ragged-both', 'out7'} | ({'channel-mask'} if _cout % 32 else set()))
+for _cin in (1, 2, 3, 4):
+    SEL_CASES['sel-tap-cin%d' % _cin] = Case(S(SEL_SMALL[0], _cin, 7 if _cin % 2 else 40, SEL_SMALL[1], SEL_SMALL[2]),
+                                              {'cin%d' % _cin, 'gen%d-sel' % (1 if _cin % 2 else 2), 'ragged-both', 'channel-mask', 'out7'})
+SEL_CASES['sel-geo-2x2'] = Case(S(1, 3, GEOMETRY_COUT, 2, 2), {'gen1-sel', 'one-tile-image', 'ragged-both'})          # one window per channel
+SEL_CASES['sel-geo-20x36'] = Case(S(3, 3, GEOMETRY_COUT, 20, 36), {'gen1-sel', 'batch', 'multi-tile-image', 'ragged-both', 'ragged-right', 'ragged-bottom', 'whole-tile'})
+SEL_CASES['sel-window'] = Case(S(SEL_SMALL[0], 3, 32, SEL_SMALL[1], SEL_SMALL[2], **WINDOW), {'gen1-sel', 'ld>cout', 'ld%4', 'channel-offset', 'ragged-both'})
+SEL_CASES['sel-gwalk4-cin3'] = Case(GEN_WALK_CASES['gwalk4-cin3'].c._replace(scale=False, shift=False, slope=1.0, sel=True),
+                                    {'gen1-sel', 'cin3', 'walk4', 'uneven-walk', 'buffer-reuse'})
+SEL_RANDOM_MAX_B = 4             # the random regime runs the small cases: those of at most this batch
+
+# ---- refusals of the sel entry: one case per `return` (and per condition of a return that has several), in order - the entry's own, then the shared body's
+SEL_REFUSALS = collections.OrderedDict([
+    ('sel-gamma-null', (S(2, 3, 20, 18, 34, nog=True), EINVAL)),
+    ('sel-z-null', (S(2, 3, 20, 18, 34, 'ps'), EINVAL)),
+    ('sel-zsel-null', (S(2, 3, 20, 18, 34, 'ys'), EINVAL)),
+    ('sel-x-null', (S(2, 3, 20, 18, 34, nox=True), EINVAL)),
+    ('sel-w-null', (S(2, 3, 20, 18, 34, now=True), EINVAL)),
+    ('sel-batch-0', (S(0, 3, 20, 18, 34), ENOSUP)),
+    ('sel-cin-5', (S(2, 5, 20, 18, 34), ENOSUP)),
+    ('sel-cout-65', (S(2, 3, 65, 18, 34), ENOSUP)),
+    ('sel-ldz<cout', (S(2, 3, 20, 18, 34, ypad=-1), EINVAL)),
+    ('sel-ldzs<cout', (S(2, 3, 20, 18, 34, ppad=-1), EINVAL)),
+    ('sel-odd-height', (S(2, 3, 20, 17, 34), EINVAL)),
+    ('sel-odd-width', (S(2, 3, 20, 18, 33), EINVAL)),
+    ('sel-stats+deterministic', (S(2, 3, 20, 18, 34, det=True), ENOSUP)),
+    ('sel-stats+deterministic-aligned', (S(2, 3, 32, 32, 64, det=True), ENOSUP)),
+    ('sel-tiles>=2^31', (S((1 << 30) + 1, 3, 20, 18, 2), EINVAL)),          # 2 tiles per image, H and W even
+])
+SEL_REFUSAL_RETURNS = collections.OrderedDict([
+    ('gamma != nullptr && z != nullptr && z_sel != nullptr', ('sel-gamma-null', 'sel-z-null', 'sel-zsel-null')),
+    ('x_nchw == nullptr', ('sel-x-null', 'sel-w-null')),                      # (`nothing to write` cannot be asked of this entry: z is required)
+    ('B <= 0', ('sel-batch-0', 'sel-cin-5', 'sel-cout-65')),
+    ('y != nullptr && ldy < Cout', ('sel-ldz<cout',)),
+    ('y_pool != nullptr', ('sel-ldzs<cout', 'sel-odd-height', 'sel-odd-width')),
+    ('stats != nullptr && y2_det.on', ('sel-stats+deterministic', 'sel-stats+deterministic-aligned')),
+    ('tiles <= 0', ('sel-tiles>=2^31',)),
+])
+
+
+def sel_first_refusing_test(c):
+    """first_refusing_test for a y2_conv0_fwd_sel call: index into SEL_REFUSAL_RETURNS."""
+    if c.nog or 'y' not in c.outs or 'p' not in c.outs:
+        return 0
+    return 1 + first_refusing_test(c)

@@ -1,6 +1,8 @@
 """CPU check of the first-layer forward case tables (tests/conv0_cases.py): the mirror of y2_conv0_fwd / launch0 agrees with what every case claims to
 reach, and the tables as a whole reach every straight-line variant, the general kernel with every Cin x NBLK, every walk length of the persistent
 grid for both kernel forms, ragged-right / ragged-bottom / ragged-both tiles and every refusal.
+The same for y2_conv0_fwd_sel (SEL_CASES, SEL_REFUSALS; tests/test_gpu_conv0_sel.py runs them): the ninth straight-line variant, which is launched
+outside the Y2_C0 list, the general kernel with `sel` through every way a call with gamma misses that variant, and the entry's refusals.
 
 Unlike fwd_cases, this mirror cannot be pinned to the built library: all variants launch as `conv0_kernel` and the entry point answers no size query,
 so nothing exported tells which variant ran.  What can be pinned is pinned to the source text below (the constants and the list of straight-line
@@ -13,7 +15,7 @@ import pytest
 import conv0_cases as cc
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'yolo2-pytorch_amd', 'csrc')
-ALL = [(n, c) for t in cc.PARITY_TABLES for n, c in t.items()]
+ALL = [(n, c) for t in cc.PARITY_TABLES + (cc.SEL_CASES,) for n, c in t.items()]
 
 
 def reached(cell, tables=cc.PARITY_TABLES, also=()):
@@ -39,6 +41,15 @@ def test_mirror_constants_are_the_sources():
     got = [(int(nb), int(out), raw == 'true') for nb, out, raw in re.findall(r'Y2_C0\((\d), (\d), (true|false)\);', src)]
     assert got == list(cc.VARIANTS)
     assert 'if (CIN == 3 && (a.H % TH) == 0 && (a.W % TW) == 0 && (a.Cout == 32 || a.Cout == 64) && (a.y == nullptr || a.ldy == a.Cout) && (a.y_pool == nullptr || a.ldp == a.Cout))' in src
+    # the ninth straight-line launch stands outside the Y2_C0 list: its condition, its instantiation (named once), and the rule that no other call with pool_sign
+    # takes a straight-line variant
+    assert 'if (a.pool_sign != nullptr && a.Cout == 32 && out == 7 && raw) {' in src and cc.SEL_VARIANT == (1, 7, True)
+    assert re.findall(r'\(conv0_kernel<3, (\d), (\d), true, (true|false)>\), dim3', src) == [('1', '7', 'true')]
+    assert src.index('if (a.pool_sign != nullptr && a.Cout == 32') < src.index('if (a.pool_sign != nullptr) done = false;') < src.index('else if (a.Cout == 32) {') < src.index('if (done) {')
+    assert 'const bool sel = (OUT == 7 && RAW) ? true : (OUT < 0 ? a.pool_sign != nullptr : false);' in src          # which kernels select: <.., 7, .., RAW> and the general one
+    assert ('return (gamma != nullptr && z != nullptr && z_sel != nullptr) ? conv0_fwd_impl(x_nchw, w, nullptr, nullptr, z, z_sel, stats, B, H, W, Cin, Cout, ldz, ldzs, 1.f, stream, gamma)'
+            in src and list(cc.SEL_REFUSAL_RETURNS)[0] == 'gamma != nullptr && z != nullptr && z_sel != nullptr' and list(cc.SEL_REFUSAL_RETURNS)[1:] == list(cc.REFUSAL_RETURNS))
+    assert 'stats may be NULL' in header
     assert 'const bool mono = a.slope >= 0.f && a.slope <= 1.f;' in src and 'a.scale == nullptr && a.shift == nullptr && a.slope == 1.f;' in src
     for name, val in (('Y2_OK', cc.OK), ('Y2_EINVAL', cc.EINVAL), ('Y2_EALIGN', cc.EALIGN), ('Y2_ENOSUP', cc.ENOSUP)):
         assert re.search(r'%s\s*=?\s*\(?(-?\d+)' % name, header) and int(re.search(r'%s\s*=?\s*\(?(-?\d+)' % name, header).group(1)) == val, name
@@ -68,6 +79,13 @@ def test_mirror_known_answers():
     assert cc.variant_name(cc.route(cc.C(2, 3, 32, 32, 64, 'p', ypad=4))) == 'sl1-o2'                                        # ldy of an absent y does not count
     assert cc.variant_name(cc.route(cc.C(2, 3, 32, 32, 64, 'y', ppad=4))) == 'sl1-o1'
     assert cc.variant_name(cc.route(cc.C(2, 3, 32, 32, 65, 'y'))) == 'gen1' and cc.variant_name(cc.route(cc.C(2, 2, 32, 32, 64, 'y'))) == 'gen1'
+    # y2_conv0_fwd_sel: the training forward at batch 64 takes the ninth variant; without statistics, at Cout 64 or into wider rows it is the general kernel
+    r = cc.route(cc.S(64, 3, 32, 416, 416))
+    assert cc.variant_name(r) == 'sl1-o7-raw-sel' and (r.ntiles, r.walk_max, r.full, r.raw, r.sel) == (21632, 11, True, True, True)
+    assert cc.variant_name(cc.route(cc.S(64, 3, 32, 416, 416, 'yp'))) == 'gen1-sel' and cc.variant_name(cc.route(cc.S(64, 3, 64, 416, 416))) == 'gen2-sel'
+    assert cc.variant_name(cc.route(cc.S(64, 3, 32, 416, 416, ppad=32))) == 'gen1-sel' and cc.variant_name(cc.route(cc.S(64, 3, 32, 418, 416))) == 'gen1-sel'
+    # the same call through the plain entry (no gamma) keeps its straight-line form
+    assert cc.variant_name(cc.route(cc.S(2, 3, 32, 32, 64, 'yp')._replace(sel=False))) == 'sl1-o3'
 
 
 # ------------------------------------------------------------------------------------------------ claims
@@ -201,3 +219,67 @@ def test_removing_a_sole_case_is_noticed():
     assert reached('straight walk7+') == ['sl1-o2-walk7'] and reached('general walk7+') == ['gwalk7-cin3']
     assert reached('cin2 walk4', (cc.GEN_WALK_CASES,)) == ['gwalk4-cin2']
     assert all(len(v) >= 1 for v in cc.REFUSAL_RETURNS.values()) and len(cc.REFUSAL_RETURNS['y != nullptr && ldy < Cout']) == 1
+
+
+# ------------------------------------------------------------------------------------------------ y2_conv0_fwd_sel
+def sel_reached(cell, without=None):
+    return reached(cell, ({n: c for n, c in cc.SEL_CASES.items() if n != without},))
+
+
+def test_sel_tables_reach_every_selecting_kernel_and_every_way_to_it():
+    assert len(cc.VARIANTS) == 8 and cc.SEL_VARIANT not in cc.VARIANTS          # the macro list, and the ninth variant counted separately
+    assert {cc.variant_name(cc.route(c.c)) for c in cc.SEL_CASES.values()} == {'sl1-o7-raw-sel', 'gen1-sel', 'gen2-sel'}
+    assert all(c.c.sel and 'sel' in cc.claims_of(c.c) for c in cc.SEL_CASES.values())
+    assert sel_reached('sl1-o7-raw-sel walk1 whole-tile') == ['sel-sl-small'] and sel_reached('sl1-o7-raw-sel walk3 steady-state uneven-walk') == ['sel-sl-walk3']
+    assert cc.SEL_CASES['sel-sl-small'].c[:5] + cc.SEL_CASES['sel-sl-walk3'].c[:5] == tuple(x for s in ('small', 'walk3') for x in (cc.ALIGNED_SIZES[s][0][0], 3, 32) + cc.ALIGNED_SIZES[s][0][1:])
+    # the stats-less aligned call: the shipped first layer on whole tiles, dense rows; with statistics it is the ninth variant, without gamma sl1-o3
+    bug = cc.SEL_CASES['sel-nostats-aligned'].c
+    assert (bug.B, bug.cin, bug.cout, bug.H, bug.W, bug.outs, bug.ypad, bug.ppad) == (1, 3, 32, 16, 32, 'yp', 0, 0) and cc.looks_aligned(bug)
+    assert sel_reached('gen1-sel fallthrough out3') == ['sel-nostats-aligned']
+    assert cc.variant_name(cc.route(bug._replace(outs='yps'))) == 'sl1-o7-raw-sel' and cc.variant_name(cc.route(bug._replace(sel=False))) == 'sl1-o3'
+    # each fall-through differs from the ninth variant's call in one respect
+    for name, field, value in (('sel-fall-cout64', 'cout', 32), ('sel-fall-ldz', 'ypad', 0), ('sel-fall-ldzs', 'ppad', 0), ('sel-fall-cin4', 'cin', 3), ('sel-nostats-aligned', 'outs', 'yps')):
+        c = cc.SEL_CASES[name].c
+        assert cc.route(c).kernel == 'general' and cc.variant_name(cc.route(c._replace(**{field: value}))) == 'sl1-o7-raw-sel', name
+    assert sel_reached('gen2-sel fallthrough out7') == ['sel-fall-cout64'] and sel_reached('gen2-sel out3') == ['sel-fall-cout64-nostats']
+    assert [n for n in sel_reached('gen1-sel fallthrough ld>cout')] == ['sel-fall-ldz', 'sel-fall-ldzs']
+    assert sel_reached('gen1-sel cin4 whole-tile') == ['sel-fall-cin4']
+    # the general kernel: channel masks, tap tables, geometry, the window form, a persistent walk
+    assert [c.c.cout for n, c in cc.SEL_CASES.items() if n.startswith('sel-mask-')] == list(cc.MASK_COUTS) == [1, 31, 32, 33, 63, 64]
+    for cout in cc.MASK_COUTS:
+        c = cc.SEL_CASES['sel-mask-cout%d' % cout].c
+        assert c[:5] == (2, 3, cout, 18, 34) and cc.route(c).nblk == (1 if cout <= 32 else 2) and c.outs == 'yps'
+    for cin in (1, 2, 3, 4):
+        assert 'sel-tap-cin%d' % cin in sel_reached('cin%d ragged-both out7' % cin)
+        assert cin == 3 or sel_reached('cin%d ragged-both' % cin, without='sel-tap-cin%d' % cin) == []          # (Cin 3 is everywhere; the others have this case alone)
+        assert cc.SEL_CASES['sel-tap-cin%d' % cin].c[3:5] == (18, 34)
+    assert {cc.route(cc.SEL_CASES['sel-tap-cin%d' % cin].c).nblk for cin in (1, 2, 3, 4)} == {1, 2}
+    assert cc.SEL_CASES['sel-geo-2x2'].c[3:5] == (2, 2) and cc.SEL_CASES['sel-geo-20x36'].c[3:5] == (20, 36)
+    assert sel_reached('gen1-sel one-tile-image ragged-both', without='sel-geo-2x2') == [] and sel_reached('gen1-sel ragged-bottom ragged-right whole-tile', without='sel-geo-20x36') == []
+    w = cc.SEL_CASES['sel-window'].c
+    assert (w.ypad, w.yoff, w.ppad, w.poff) == (5, 3, 6, 1) and sel_reached('gen1-sel channel-offset ld%4') == ['sel-window']
+    assert sel_reached('gen1-sel walk4 buffer-reuse uneven-walk') == ['sel-gwalk4-cin3'] and cc.SEL_CASES['sel-gwalk4-cin3'].c[:5] == cc.GEN_WALK_CASES['gwalk4-cin3'].c[:5]
+    # the random regime runs what is small; only the two walks are not
+    assert [n for n, c in cc.SEL_CASES.items() if c.c.B > cc.SEL_RANDOM_MAX_B] == ['sel-sl-walk3', 'sel-gwalk4-cin3']
+
+
+def test_sel_refusals_one_per_return_in_the_entry_point_s_order():
+    listed = [n for names in cc.SEL_REFUSAL_RETURNS.values() for n in names]
+    assert listed == list(cc.SEL_REFUSALS)
+    base = cc.S(2, 3, 20, 18, 34)
+    assert cc.route(base).rc == cc.OK and cc.variant_name(cc.route(base)) == 'gen1-sel'
+    for i, (key, names) in enumerate(cc.SEL_REFUSAL_RETURNS.items()):
+        assert names, key
+        for n in names:
+            c, rc = cc.SEL_REFUSALS[n]
+            assert cc.is_sel_entry(c) and cc.route(c).rc == rc != cc.OK, n
+            assert cc.sel_first_refusing_test(c) == i, n
+            diff = [f for f in c._fields if getattr(c, f) != getattr(base, f)]
+            assert 1 <= len(diff) <= (5 if n in ('sel-tiles>=2^31', 'sel-stats+deterministic-aligned') else 2 if n == 'sel-gamma-null' else 1), (n, diff)
+    assert {n for n in listed if 'odd' in n} == {'sel-odd-height', 'sel-odd-width'} and 'sel-ldzs<cout' in listed and 'sel-stats+deterministic' in listed
+    assert cc.route(cc.SEL_REFUSALS['sel-stats+deterministic'][0]._replace(det=False)).rc == cc.OK
+    assert cc.route(cc.SEL_REFUSALS['sel-stats+deterministic'][0]._replace(outs='yp')).rc == cc.OK          # deterministic mode without statistics: accepted
+    assert cc.variant_name(cc.route(cc.SEL_REFUSALS['sel-stats+deterministic-aligned'][0]._replace(det=False))) == 'sl1-o7-raw-sel'
+    assert cc.route(cc.SEL_REFUSALS['sel-tiles>=2^31'][0]._replace(B=(1 << 30) - 1)).rc == cc.OK
+    # the entry's own refusal comes first: gamma NULL with x NULL, Cin 5 or an odd height is still EINVAL
+    assert cc.route(cc.S(2, 5, 20, 18, 34, nog=True)).rc == cc.EINVAL and cc.route(cc.S(2, 5, 20, 18, 34)).rc == cc.ENOSUP

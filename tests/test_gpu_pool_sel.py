@@ -1,6 +1,8 @@
 """Pooled blocks keep z_sel, the one pre-activation per 2x2 window that the pool selects: the producer of z_sel against its definition,
 the forward over z_sel against the pooled forward over z (bit for bit), pass 1 of the BatchNorm backward from (z_sel, dy_pool) against fp64 autograd,
-and a Darknet training step with the path on, off and forced onto the activation kernel's producer.
+a Darknet training step with the path on, off and forced onto the activation kernel's producer, and - the second half of the file - every dispatch path of
+y2_bn_act_fwd_sel and y2_bn_act_bwd_sel (tests/pool_sel_cases.py) against the definition and fp64 autograd.  The first layer's own producer,
+y2_conv0_fwd_sel, has its dispatch paths in tests/test_gpu_conv0_sel.py.
 Every gamma vector has both signs and an exact zero; constructed inputs hold windows with two equal extremes and windows whose extreme is -0 / +0."""
 import numpy as np
 import pytest
@@ -283,3 +285,275 @@ def test_training_step_with_the_path_on_off_and_forced(step_oracle, monkeypatch)
         for k in o['ref']:
             e = rel(grads[a][k], grads[b][k].cpu())
             assert e <= o['bound'][k], (a, b, k, e)
+
+
+# ================================================================================================ every dispatch path of the two streaming entries
+# tests/pool_sel_cases.py holds the cases and the mirror of bn_act_fwd_impl / bn_act_bwd_impl (checked on the CPU by tests/test_pool_sel_cases.py).
+# Inputs: z is a multiple of 1 / 64 in [-4, 4] (513 values) plus constructed_z's tie and -0 / +0 windows; with |scale| >= 0.25 two different z of a window
+# never round to one activation, so `z at the first maximal activation` (what the kernels compute) and the header's definition select the same element in EVERY
+# window - the number of windows where they could differ is asserted to be 0; it is a condition of the inputs, not a tolerance.  Every map is a channel window
+# of rows of -7.0 between -7.0 guards, its base pointer on or one float off a 16-byte boundary as the case says.
+import ctypes
+import functools
+
+import pool_sel_cases as pc
+from test_gpu_conv0_sel import definition
+from test_gpu_streaming import BN_EPS, TOL, TOL_DZ
+from test_gpu_wgrad import GUARD, SENT, deterministic, kernels_of
+
+SUM_TOL = dict(rtol=1e-4, atol=1e-4)          # the sums' bound of test_pass1_from_z_sel_matches_fp64_autograd above
+
+
+class Map(object):
+    """rows x ld floats of -7.0 between two guards; the data (or the destination) is the channel window off .. off + C; the base pointer lies `mis` floats
+    past a 16-byte boundary."""
+
+    def __init__(self, rows, C, ld, off=0, mis=0, data=None):
+        self.flat = torch.full((GUARD + 4 + rows * ld + GUARD,), SENT, dtype=torch.float32, device=dev())
+        self.start, self.rows, self.C, self.ld, self.off = GUARD + mis, rows, C, ld, off
+        self.view = self.flat[self.start:self.start + rows * ld].view(rows, ld)
+        self.win = self.view[:, off:off + C]
+        if data is not None:
+            self.win.copy_(data.reshape(rows, C))
+        self.ptr = ctypes.c_void_p(self.flat.data_ptr() + 4 * self.start)
+        assert (self.ptr.value % 16 != 0) == bool(mis)
+        self.before = self.flat.clone()
+
+    def unchanged(self):
+        return torch.equal(self.flat.view(torch.int32), self.before.view(torch.int32))
+
+    def outside_intact(self):
+        """Everything but the channel window still holds the sentinel."""
+        m = self.flat.clone()
+        m[self.start:self.start + self.rows * self.ld].view(self.rows, self.ld)[:, self.off:self.off + self.C] = SENT
+        return bool((m == SENT).all())
+
+
+def grid_z(Bc, Hc, Wc, C, g):
+    """[B,H,W,C] fp32: multiples of 1 / 64 in [-4, 4], with constructed_z's windows: two equal maxima, two equal minima, a -0 / +0 pair at either extreme."""
+    z = torch.randint(-256, 257, (Bc, Hc, Wc, C), generator=g).float() / 64
+    if Bc >= 2 and Hc >= 4 and Wc >= 4:
+        z[0, 0, 0] = z[0, 1, 1] = 4.0
+        z[0, 2, 3] = z[0, 3, 2] = -4.0
+        z[1, 0:2, 0:2] = -1.0
+        z[1, 0, 0], z[1, 0, 1] = -0.0, 0.0
+        z[1, 2:4, 2:4] = 1.0
+        z[1, 2, 2], z[1, 2, 3] = 0.0, -0.0
+    return z
+
+
+def signed(C, g, lo, hi):
+    """|v| in [lo, hi], signs alternating in pairs, v[1] = 0 and v[2] = -0.0: both signs, an exact zero and a -0.0."""
+    v = lo + (hi - lo) * torch.rand(C, generator=g, dtype=torch.float64)
+    v[(torch.arange(C) // 2) % 2 == 1] *= -1.0
+    v[1], v[2] = 0.0, -0.0
+    v = v.float()
+    assert bool((v > 0).any()) and bool((v < 0).any()) and v[1:3].view(torch.int32).tolist() == [0, -(1 << 31)]
+    return v
+
+
+def windows_where_the_rules_could_differ(z, scale, shift, slope):
+    """Windows (per channel with a non-zero scale) in which two DIFFERENT z have the same fp32 activation: there `first maximal activation` may pick another
+    element than the definition.  (A zero scale maps every z to one activation: both rules keep the first element.)"""
+    v = F.leaky_relu(z * scale + shift, slope)                    # fp32, one rounding per operation, as the kernel
+    zq = [z[:, i::2, j::2] for i in (0, 1) for j in (0, 1)]
+    vq = [v[:, i::2, j::2] for i in (0, 1) for j in (0, 1)]
+    bad = torch.zeros_like(zq[0], dtype=torch.bool)
+    for a in range(4):
+        for b in range(a + 1, 4):
+            bad |= (vq[a] == vq[b]) & (zq[a] != zq[b])
+    return int(bad[..., scale != 0].sum())
+
+
+def pooled(c):
+    return c.B * (c.H // 2) * (c.W // 2)
+
+
+# ------------------------------------------------------------------------------------------------ forward
+def fwd_call(c, z, scale, shift, yp, zs, sel=True):
+    import _hip
+    L = _hip.lib()
+    s = pc.strides(c)
+    nul = lambda name, p: None if name in c.null else p
+    sc, sh = (_hip.ptr(scale), _hip.ptr(shift)) if c.affine else (None, None)
+    if sel:
+        return L.y2_bn_act_fwd_sel(nul('z', z.ptr), sc, sh, 0.1, nul('y_pool', yp.ptr), nul('z_sel', zs.ptr), c.B, c.H, c.W, c.C, s['ldz'], s['ldp'], c.poff, s['ldzs'], _hip.stream())
+    return L.y2_bn_act_fwd(z.ptr, sc, sh, 0.1, None, yp.ptr, c.B, c.H, c.W, c.C, s['ldz'], 0, 0, s['ldp'], c.poff, 0, _hip.stream())
+
+
+@pytest.mark.parametrize('name', list(pc.FWD_CASES))
+def test_bn_act_fwd_sel_paths(name):
+    """z_sel bit-equal to the header's definition, y_pool bit-equal to the plain pooled launch's and within TOL of fp64 max_pool2d(leaky_relu(batch_norm))."""
+    c = pc.FWD_CASES[name].c
+    r = pc.fwd_route(c)
+    assert r.rc == pc.OK
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    z = grid_z(c.B, c.H, c.W, c.C, g)
+    scale = signed(c.C, g, 0.25, 1.5) if c.affine else torch.ones(c.C)
+    shift = (0.1 + 0.2 * torch.rand(c.C, generator=g, dtype=torch.float64)).float() if c.affine else torch.zeros(c.C)
+    assert windows_where_the_rules_could_differ(z, scale, shift, 0.1) == 0
+    s = pc.strides(c)
+    zm = Map(c.B * c.H * c.W, c.C, s['ldz'], 0, c.zmis, z.to(dev()))
+    sd, hd = scale.to(dev()), shift.to(dev())
+    out = {}
+    for sel in (True, False):
+        yp = Map(pooled(c), c.C, s['ldp'], c.poff, c.pmis)
+        zs = Map(pooled(c), c.C, s['ldzs'], 0, c.smis)
+        names = kernels_of(lambda: out.__setitem__('rc', fwd_call(c, zm, sd, hd, yp, zs, sel)))
+        assert out['rc'] == 0 and names == ['bn_act_fwd_kernel']
+        assert yp.outside_intact() and zs.outside_intact() and zm.unchanged() and (sel or zs.unchanged())
+        out[sel] = (yp.win.clone(), zs.win.clone())
+    want = definition(z.to(dev()), sd).reshape(-1, c.C)
+    assert torch.equal(out[True][1].view(torch.int32), want.view(torch.int32)), 'z_sel is not the definition'
+    assert torch.equal(out[True][0].view(torch.int32), out[False][0].view(torch.int32)), 'y_pool differs from the plain pooled launch\'s'
+    z64 = z.double().permute(0, 3, 1, 2)
+    ref = F.max_pool2d(F.leaky_relu(F.batch_norm(z64, torch.zeros(c.C, dtype=torch.float64), torch.ones(c.C, dtype=torch.float64) - BN_EPS, scale.double(), shift.double(), False, 0.0, BN_EPS), 0.1), 2)          # (running variance 1 - eps: the affine z * scale + shift)
+    e = rel(out[True][0].view(c.B, c.H // 2, c.W // 2, c.C).permute(0, 3, 1, 2), ref)
+    print('y_pool against fp64: %.3g x rms' % e)
+    assert e <= TOL
+
+
+@pytest.mark.parametrize('name', list(pc.FWD_REFUSALS))
+def test_bn_act_fwd_sel_refusals(name):
+    """Every pointer is valid but the one under test; a refusal writes nothing."""
+    c, rc = pc.FWD_REFUSALS[name]
+    assert pc.fwd_route(c).rc == rc
+    maps = [Map(64, 8, 16) for _ in range(3)]
+    sc = torch.ones(16, device=dev())
+    assert fwd_call(c, maps[0], sc, sc, maps[1], maps[2]) == rc
+    torch.cuda.synchronize()
+    assert all(m.unchanged() for m in maps)
+
+
+# ------------------------------------------------------------------------------------------------ backward
+@functools.lru_cache(maxsize=4)
+def bwd_reference(Bc, Hc, Wc, C):
+    """Inputs of one geometry and the fp64 autograd of max_pool2d(leaky_relu(batch_norm(z))), shared (read only) by the cases of that geometry."""
+    g = torch.Generator().manual_seed(Bc + 3 * Hc + 5 * Wc + 7 * C)
+    z = grid_z(Bc, Hc, Wc, C, g)
+    gamma = signed(C, g, 0.75, 1.5)
+    beta = (0.1 + 0.2 * torch.rand(C, generator=g, dtype=torch.float64)).float()
+    dyp = torch.randn(Bc, C, Hc // 2, Wc // 2, generator=g, dtype=torch.float32)
+    z64 = z.double().permute(0, 3, 1, 2).contiguous()
+    with torch.no_grad():
+        _, mean, invstd = torch.native_batch_norm(z64, gamma.double(), beta.double(), None, None, True, 0.0, BN_EPS)
+        zhat = (z64 - mean.view(1, -1, 1, 1)) * invstd.view(1, -1, 1, 1)
+        # LeakyReLU's derivative jumps at 0: a channel with a pre-activation within 1e-3 of 0 gets another beta (neighbouring pre-activations lie |scale| / 64 >= 0.004 apart)
+        for _ in range(16):
+            pre = zhat * gamma.double().view(1, -1, 1, 1) + beta.double().view(1, -1, 1, 1)
+            close = (pre.abs() < 1e-3).flatten(2).any(2).any(0)
+            if not bool(close.any()):
+                break
+            beta[close] += 0.002
+        assert pre.abs().min().item() >= 1e-3, 'test input: a pre-activation sits on the LeakyReLU kink'
+    scale = (gamma.double() * invstd).float()
+    shift = (beta.double() - mean * gamma.double() * invstd).float()
+    assert float(scale[scale != 0].abs().min()) >= 0.25 and windows_where_the_rules_could_differ(z, scale, shift, 0.1) == 0
+    zr = z64.clone().requires_grad_(True)
+    ga, be = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    yp = F.max_pool2d(F.leaky_relu(F.batch_norm(zr, None, None, ga, be, True, 0.0, BN_EPS), 0.1), 2)
+    (yp * dyp.double()).sum().backward()
+    return dict(z=z, gamma=gamma, dyp=dyp, mean=mean.float(), invstd=invstd.float(), scale=scale, shift=shift, dz=zr.grad, dbeta=be.grad.numpy(), dgamma=ga.grad.numpy())
+
+
+class BwdRun(object):
+    """One y2_bn_act_bwd_sel call (sel=False: the pooled-only y2_bn_act_bwd on the same operands) on fresh buffers."""
+
+    def __init__(self, c, ref, sel=True, alloc=None):
+        import _hip
+        L = _hip.lib()
+        d = dev()
+        call_c, c = c, alloc or c                                     # (alloc: a refusal - the buffers are built for `alloc`, the call carries c)
+        s = pc.strides(c)
+        C, rows, prow = c.C, c.B * c.H * c.W, pooled(c)
+        self.held = {k: ref[k].to(d) for k in ('scale', 'shift', 'mean', 'invstd', 'gamma')}
+        zd = ref['z'].to(d)
+        self.z = Map(rows, C, s['ldz'], 0, c.zmis, zd)
+        zs = definition(zd, self.held['gamma'])
+        self.dyp = Map(prow, C, s['ldp'], c.poff, c.pmis, ref['dyp'].permute(0, 2, 3, 1).to(d))
+        if c.dz == 'alias':          # one allocation: z_sel in its first quarter, dz over all of it
+            assert s['ldzs'] == C and s['ldd'] == C
+            self.dz = Map(rows, C, C, 0, c.smis)
+            self.dz.view[:prow].copy_(zs.reshape(prow, C))
+            self.zs = None
+            zs_ptr = self.dz.ptr
+        else:
+            self.zs = Map(prow, C, s['ldzs'], 0, c.smis, zs)
+            zs_ptr = self.zs.ptr
+            self.dz = Map(rows, C, s['ldd'], 0, c.dmis) if c.dz != 'null' else None
+        self.sums = torch.full((2 * C + 4,), SENT, dtype=torch.float64, device=d)
+        self.sums[:2 * C] = 0.0
+        nul = lambda name, p: None if name in c.null else p
+        h = {k: _hip.ptr(v) for k, v in self.held.items()}
+        dzp = self.dz.ptr if self.dz is not None else None
+        c, s, C = call_c, pc.strides(call_c), call_c.C
+
+        def call():
+            if sel:
+                self.rc = L.y2_bn_act_bwd_sel(nul('z', self.z.ptr), nul('z_sel', zs_ptr), s['ldzs'], h['scale'], h['shift'], nul('mean', h['mean']), nul('invstd', h['invstd']), nul('gamma', h['gamma']),
+                                              0.1, nul('dy_pool', self.dyp.ptr), s['ldp'], c.poff, nul('sums', _hip.ptr(self.sums)), dzp, s['ldd'], c.B, c.H, c.W, C, s['ldz'], _hip.stream())
+            else:
+                self.rc = L.y2_bn_act_bwd(self.z.ptr, h['scale'], h['shift'], h['mean'], h['invstd'], h['gamma'], 0.1, None, 0, 0, 0, self.dyp.ptr, s['ldp'], c.poff,
+                                          _hip.ptr(self.sums), dzp, s['ldd'], c.B, c.H, c.W, C, s['ldz'], 1, _hip.stream())
+        self.kernels = kernels_of(call)
+
+    def intact(self):
+        return (self.z.unchanged() and self.dyp.unchanged() and (self.zs is None or self.zs.unchanged()) and (self.dz is None or self.dz.outside_intact())
+                and bool((self.sums[-4:] == SENT).all()))
+
+
+def check_bwd(c, ref, run):
+    C = c.C
+    assert run.rc == 0 and run.intact()
+    got = run.sums[:2 * C].cpu().numpy()
+    print('max |sum error| %.3g' % np.abs(got - np.concatenate([ref['dbeta'], ref['dgamma']])).max())
+    np.testing.assert_allclose(got[:C], ref['dbeta'], **SUM_TOL)
+    np.testing.assert_allclose(got[C:], ref['dgamma'], **SUM_TOL)
+    if run.dz is not None:
+        e = rel(run.dz.win.view(c.B, c.H, c.W, C).permute(0, 3, 1, 2), ref['dz'])
+        print('dz against fp64: %.3g x rms' % e)
+        assert e <= TOL_DZ
+
+
+@pytest.mark.parametrize('name', list(pc.BWD_CASES))
+def test_bn_act_bwd_sel_paths(name):
+    """Sums and dz against fp64 autograd, and the reduction form the mirror names, observed by kernel name: the block-reduce kernel exactly when the partial
+    sums are parked, the det-reduce kernel exactly in deterministic mode.  Deterministic mode: a second run is bit-identical, and the sums are those of the
+    pooled-only y2_bn_act_bwd bit for bit (the same grid, the same loop order, a sum that differs only by zero terms: DESIGN.md 3.4)."""
+    import _hip
+    c = pc.BWD_CASES[name].c
+    r = pc.bwd_route(c)
+    assert r.rc == pc.OK
+    ref = bwd_reference(c.B, c.H, c.W, c.C)
+    want = ['bn_act_bwd_kernel'] + {'atomics': [], 'parked': ['bn_bwd_block_reduce_kernel'], 'det': ['det_reduce_rows_kernel']}[r.form] + (['bn_act_bwd_kernel'] if c.dz != 'null' else [])
+    if not c.det:
+        run = BwdRun(c, ref)
+        assert run.kernels == want, (run.kernels, r)
+        check_bwd(c, ref, run)
+        return
+    with deterministic():
+        a, b, full = BwdRun(c, ref), BwdRun(c, ref), BwdRun(c, ref, sel=False)
+    assert not _hip.lib().y2_get_deterministic()
+    assert a.kernels == b.kernels == full.kernels == want, (a.kernels, full.kernels)
+    for run in (a, b, full):
+        check_bwd(c, ref, run)
+    assert torch.equal(a.sums.view(torch.int64), b.sums.view(torch.int64)) and (a.dz is None or torch.equal(a.dz.flat.view(torch.int32), b.dz.flat.view(torch.int32))), 'two deterministic runs differ'
+    assert torch.equal(a.sums.view(torch.int64), full.sums.view(torch.int64)), 'deterministic sums from z_sel are not the pooled-only backward\'s, bit for bit'
+    assert a.dz is None or torch.equal(a.dz.flat.view(torch.int32), full.dz.flat.view(torch.int32))
+
+
+@pytest.mark.parametrize('name', list(pc.BWD_REFUSALS))
+def test_bn_act_bwd_sel_refusals(name):
+    """Every pointer is valid but the one under test; a refusal writes nothing."""
+    import _hip
+    c, rc = pc.BWD_REFUSALS[name]
+    assert pc.bwd_route(c).rc == rc
+    if c.det_small:
+        with deterministic(pc.DET_SMALL_BYTES):
+            run = BwdRun(c, bwd_reference(c.B, c.H, c.W, c.C))
+        assert not _hip.lib().y2_get_deterministic()
+    else:
+        alloc = pc.K()                                                 # what the buffers are built for; the call carries c's sizes, strides and NULLs
+        run = BwdRun(c, bwd_reference(alloc.B, alloc.H, alloc.W, alloc.C), alloc=alloc)
+    assert run.rc == rc and run.kernels == []
+    assert run.intact() and (run.dz is None or run.dz.unchanged()) and not bool(run.sums[:-4].any())

@@ -350,7 +350,8 @@ int launch0(const Conv0Args& a, hipStream_t s) {
         }
 #define Y2_C0(NB_, OUT_, RAW_) Y2_LAUNCH("conv0_kernel", flops, (conv0_kernel<3, NB_, OUT_, true, RAW_>), dim3((unsigned)grid), dim3(256), 0, s, a)
         bool done = true;
-        if (a.Cout == 32) {
+        if (a.pool_sign != nullptr) done = false;          // any other y2_conv0_fwd_sel call (stats NULL, Cout 64): no instantiation below selects, the general kernel does
+        else if (a.Cout == 32) {
             if (out == 2 && mono) Y2_C0(1, 2, false); else if (out == 5 && raw) Y2_C0(1, 5, true); else if (out == 5) Y2_C0(1, 5, false);
             else if (out == 1) Y2_C0(1, 1, false); else if (out == 3) Y2_C0(1, 3, false); else done = false;
         } else {
