@@ -30,6 +30,7 @@ def build(sd):
 
 
 def test_dp_wrapper_rccl_world1_equals_plain_backward():
+    import _hip
     import model
     import train
     s = socket.socket()
@@ -44,8 +45,7 @@ def test_dp_wrapper_rccl_world1_equals_plain_backward():
         sd = odark.init_state_dict(5, 20, seed=0, channels=widths, head_scale=1 / 8.0)
         x = synth.images(2, 96, seed=1).cuda()
         data = synth.norm_data(synth.labels(2, 96, 20, seed=2), 96, 96, 3, 3)
-        grads = []
-        for wrap in (False, True):
+        def backward_of(wrap):
             inf, anchors = build(sd)
             m = train.DataParallelRCCL(inf, bucket_bytes=4096) if wrap else inf
             if wrap:
@@ -54,7 +54,19 @@ def test_dp_wrapper_rccl_world1_equals_plain_backward():
             loss, _ = model.loss(anchors, data, pred, 0.6)
             sum(loss[k] * oloss.HPARAM[k] for k in loss).backward()
             torch.cuda.synchronize()
-            grads.append({k: p.grad.clone() for k, p in inf.named_parameters()})
+            return {k: p.grad.clone() for k, p in inf.named_parameters()}
+        # Both compared passes must run the SAME algorithms.  A first pass measures its layers with the transformed input kept (the weight gradients
+        # are unknown), the next one measures the same forward layers again under the key without it - and on a 3x3 map the direct kernel and Winograd
+        # are a coin toss: compared directly, the two passes differ by algorithm rounding (1.0-1.3e-5 at layers1.6.bn.weight), not by summation order.
+        # So: unwrapped passes until the algorithm table has settled, then the comparison, during which nothing may be measured.
+        for _ in range(4):
+            settled = len(_hip.TUNE_MISSES)
+            backward_of(False)
+            if len(_hip.TUNE_MISSES) == settled:
+                break
+        settled = len(_hip.TUNE_MISSES)
+        grads = [backward_of(False), backward_of(True)]
+        assert len(_hip.TUNE_MISSES) == settled, _hip.TUNE_MISSES[settled:]
         for k in grads[0]:
             a, b = grads[0][k], grads[1][k]
             assert (a - b).abs().max().item() <= 1e-5 * b.abs().max().item() + 1e-9, k

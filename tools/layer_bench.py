@@ -35,7 +35,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--only', default='')
     ap.add_argument('--no-split', action='store_true')
-    ap.add_argument('--wino', type=int, default=0, help='3x3 layers through algo 1 (Winograd F(2x2,3x3)) or 2 (fused GEMM + output transform); TF/s stay direct-equivalent')
+    ap.add_argument('--wino', type=int, default=0, help='3x3 layers through algorithm 1 (_hip.ALGO_WINOGRAD, F(2x2,3x3)) or 2 (_hip.ALGO_WINOGRAD_FUSED: fused GEMM + output transform); TF/s stay direct-equivalent')
     args = ap.parse_args()
     L = _hip.lib()
     dev = torch.device('cuda:0')

@@ -106,13 +106,14 @@ def main():
         if (args.only == 'wgrad' and not is_w) or (args.only == 'conv' and is_w) or hw < args.min_hw:
             continue
         if is_w:
-            alts = [c for c in ((0, 2, 1) if k[8] else (0, 2)) if c != cur]
+            alts = [c for c in ((_hip.WGRAD_DIRECT, _hip.WGRAD_WINO_F34, _hip.WGRAD_WINO) if k[8] else (_hip.WGRAD_DIRECT, _hip.WGRAD_WINO_F34)) if c != cur]
         else:
-            algo, tile = (tuple(cur) if isinstance(cur, (list, tuple)) else (0, cur))
+            algo, tile = (tuple(cur) if isinstance(cur, (list, tuple)) else (_hip.ALGO_DIRECT, cur))
             ksize, wino_ok, implicit_ok, f43 = k[6], k[18], k[19], ('f43' in k)
-            cands = [(0, t) for t in (1, 2, 3, 5)]
+            cands = [(_hip.ALGO_DIRECT, t) for t in (1, 2, 3, 5)]
             if ksize == 3 and wino_ok:
-                cands += [(1, 5), (1, 3), (2, 0), (2, 3)] + ([(3, 0), (3, 3)] if implicit_ok else []) + ([(6, 5), (6, 3)] if f43 else [])
+                cands += [(_hip.ALGO_WINOGRAD, 5), (_hip.ALGO_WINOGRAD, 3), (_hip.ALGO_WINOGRAD_FUSED, 0), (_hip.ALGO_WINOGRAD_FUSED, 3)] + ([(_hip.ALGO_WINOGRAD_IMPLICIT, 0), (_hip.ALGO_WINOGRAD_IMPLICIT, 3)] if implicit_ok else []) \
+                    + ([(_hip.ALGO_WINOGRAD_F43, 5), (_hip.ALGO_WINOGRAD_F43, 3)] if f43 else [])
             alts = [c for c in cands if tuple(c) != (algo, tile)]
         for alt in alts:
             table[k] = alt if is_w else list(alt)
@@ -177,11 +178,11 @@ def detect_descent(args, dev, table, inf, anchors):
     changed = []
     for k in keys:
         cur = table[k]
-        algo, tile = (tuple(cur) if isinstance(cur, (list, tuple)) else (0, cur))
+        algo, tile = (tuple(cur) if isinstance(cur, (list, tuple)) else (_hip.ALGO_DIRECT, cur))
         ksize, wino_ok, implicit_ok = k[6], k[18], k[19]
-        cands = [(0, t) for t in (1, 2, 3, 5)] + ([(0, t) for t in (11, 12, 13, 15)] if ksize == 1 and not k[8] else [])
+        cands = [(_hip.ALGO_DIRECT, t) for t in (1, 2, 3, 5)] + ([(_hip.ALGO_DIRECT, t) for t in _hip.PERSISTENT_TILES] if ksize == 1 and not k[8] else [])
         if ksize == 3 and wino_ok:
-            cands += [(1, 5), (1, 3), (1, 2), (2, 0), (2, 3)] + ([(3, 0), (3, 3)] if implicit_ok else [])
+            cands += [(_hip.ALGO_WINOGRAD, 5), (_hip.ALGO_WINOGRAD, 3), (_hip.ALGO_WINOGRAD, 2), (_hip.ALGO_WINOGRAD_FUSED, 0), (_hip.ALGO_WINOGRAD_FUSED, 3)] + ([(_hip.ALGO_WINOGRAD_IMPLICIT, 0), (_hip.ALGO_WINOGRAD_IMPLICIT, 3)] if implicit_ok else [])
         for alt in [c for c in cands if tuple(c) != (algo, tile)]:
             table[k] = list(alt)
             try:

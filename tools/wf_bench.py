@@ -55,8 +55,8 @@ def main():
         p.x, p.w, p.scale, p.shift, p.y = x.data_ptr(), u.data_ptr(), scale.data_ptr(), shift.data_ptr(), y.data_ptr()
         p.y_pool = yp.data_ptr() if yp is not None else None
         p.stats = stats.data_ptr() if stats is not None else None
-        p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize, p.ldy, p.ldp, p.slope, p.algo = B, H, H, cin, cin, cout, 3, cout, cout, 0.1, 2
-        p.algo, p.tile = 1, 5
+        p.B, p.H, p.W, p.Cin, p.ldx, p.Cout, p.ksize, p.ldy, p.ldp, p.slope = B, H, H, cin, cin, cout, 3, cout, cout, 0.1
+        p.algo, p.tile = _hip.ALGO_WINOGRAD, 5
         need = L.y2_conv_fwd_workspace_bytes(ctypes.byref(p))
         ws = torch.empty(need // 4 + 4, device=dev)
         p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel() * 4
@@ -65,7 +65,7 @@ def main():
         diffs = []
         for v in variants:
             os.environ['Y2_WF_VARIANT'] = str(3 if v == 100 else (32 if v == 136 else v))      # 136: third-generation kernel, implicit
-            p.algo = 3 if v in (100, 136) else (1 if v == 200 else (0 if v == 300 else 2))      # 200: three-kernel Winograd (64x128 GEMM tiles), 300: direct
+            p.algo = _hip.ALGO_WINOGRAD_IMPLICIT if v in (100, 136) else (_hip.ALGO_WINOGRAD if v == 200 else (_hip.ALGO_DIRECT if v == 300 else _hip.ALGO_WINOGRAD_FUSED))      # 200: three-kernel Winograd (64x128 GEMM tiles), 300: direct
             p.tile = 5 if v == 200 else 0
             p.w = wp.data_ptr() if v == 300 else u.data_ptr()
             y.fill_(float('nan'))

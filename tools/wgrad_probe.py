@@ -18,7 +18,7 @@ evict = torch.empty(768 << 20, dtype=torch.uint8, device=d)
 st = _hip.stream()
 fns = {'direct': lambda: _hip.check(L.y2_conv_wgrad(_hip.ptr(x), _hip.ptr(dz), _hip.ptr(dwp), B, H, W, cin, cin, cout, cout, 3, st), 'd'),
        'wino2x2': lambda: _hip.check(L.y2_wino_wgrad(_hip.ptr(x), _hip.ptr(dz), _hip.ptr(dwp), B, H, W, cin, cin, cout, cout, None, _hip.ptr(ws), ws.numel() * 4, st), 'w'),
-       'wino4x4': lambda: _hip.check(L.y2_wino_wgrad_ex(_hip.ptr(x), _hip.ptr(dz), _hip.ptr(dwp), B, H, W, cin, cin, cout, cout, None, _hip.ptr(ws), ws.numel() * 4, 2, st), 'w6')}
+       'wino4x4': lambda: _hip.check(L.y2_wino_wgrad_ex(_hip.ptr(x), _hip.ptr(dz), _hip.ptr(dwp), B, H, W, cin, cin, cout, cout, None, _hip.ptr(ws), ws.numel() * 4, _hip.WINO_WGRAD_F34, st), 'w6')}
 for name, fn in fns.items():
     fn(); torch.cuda.synchronize()
     hot = []

@@ -5,6 +5,7 @@ numerical operation on the hot path happens inside the library.  There is NO
 CPU fallback: if the library is missing, `lib()` raises, and every wrapper
 refuses non-GPU tensors.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -32,7 +33,6 @@ class ConvParams(ctypes.Structure):
                 ('w_plane', ctypes.c_int64)]
 
 
-# name -> argtypes; restype is int for everything except y2_build_info
 class OptTensor(ctypes.Structure):
     """y2_opt_tensor (include/yolo2_hip.h)."""
     _fields_ = [('param', c_void_p), ('grad', c_void_p), ('state1', c_void_p), ('state2', c_void_p), ('numel', ctypes.c_int64)]
@@ -56,6 +56,19 @@ class MultiItem(ctypes.Structure):
 
 MULTI_ZERO, MULTI_F64_TO_F32, MULTI_COPY = 0, 1, 2
 
+# Convolution algorithms of y2_conv_fwd (Y2_ALGO_*, include/yolo2_hip.h) and the groups the selection below keeps asking about
+ALGO_DIRECT, ALGO_WINOGRAD, ALGO_WINOGRAD_FUSED, ALGO_WINOGRAD_IMPLICIT, ALGO_WINOGRAD_SPLIT, ALGO_WINOGRAD_SPLIT_F16, ALGO_WINOGRAD_F43, ALGO_WINOGRAD_F43_PRE = range(8)
+ALGOS_READ_U = (ALGO_WINOGRAD, ALGO_WINOGRAD_FUSED, ALGO_WINOGRAD_IMPLICIT)       # filter operand: the y2_wino_weight output U [16][Cout][Cin]
+ALGOS_SPLIT = (ALGO_WINOGRAD_SPLIT, ALGO_WINOGRAD_SPLIT_F16)                      # filter operand: the bf16 / fp16 planes of U
+ALGOS_READ_U6 = (ALGO_WINOGRAD_F43, ALGO_WINOGRAD_F43_PRE)                        # filter operand: the y2_wino6_weight output U6 [36][Cout][Cin]
+ALGOS_WINO_2X2 = ALGOS_READ_U + ALGOS_SPLIT                                       # work in the 2x2-tile Winograd domain
+PERSISTENT_TILES = (11, 12, 13, 15)          # tile ids of the direct kernel's persistent-workgroup forms (its other tile ids have no names in the header either)
+# Weight-gradient kernels, as wgrad_choice answers and conv_wgrad runs them.  (WGRAD_F34, further down, is the Y2_WGRAD_F34 switch.)
+WGRAD_DIRECT, WGRAD_WINO, WGRAD_WINO_F34 = 0, 1, 2
+# native_layout of y2_wino_wgrad_ex / y2_wino_wgrad_workspace_bytes_ex.  Bit 0: the result is written as dw[Cout][Cin][3][3]; bit 1: Winograd F(3x3, 4x4),
+# 36 reductions over 4x4 gradient tiles; bit 2 (with bit 1): `dz` IS the transformed gradient [36][T][Cout] that y2_bn_act_bwd_wino6 wrote
+WINO_WGRAD_PACKED, WINO_WGRAD_NATIVE, WINO_WGRAD_F34, WINO_WGRAD_F34_NATIVE, WINO_WGRAD_F34_PRE, WINO_WGRAD_F34_PRE_NATIVE = 0, 1, 2, 3, 6, 7
+
 EVAL_MATCH_MAX_G = 1024      # Y2_EVAL_MATCH_MAX_G (include/yolo2_hip.h)
 COLLATE_MAX_W = 4096         # Y2_COLLATE_MAX_W
 WARP_MAX_DIM = 16384         # Y2_WARP_MAX_DIM
@@ -64,6 +77,7 @@ JPEG_MAX_DIM = 16384         # Y2_JPEG_MAX_DIM
 JPEG_DESC_BYTES = 4096       # Y2_JPEG_DESC_BYTES
 KMEANS_MAX_K = 16             # Y2_KMEANS_MAX_K
 
+# name -> argtypes, hand-written from include/yolo2_hip.h (tests/test_abi.py compares the two argument by argument); restype: lib()
 SIGNATURES = {
     'y2_abi_version': [],
     'y2_pack_weight': [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
@@ -512,9 +526,13 @@ def save_tune_defaults(path=None, note=''):
 
 WINOGRAD = os.environ.get('Y2_WINOGRAD', '1') != '0'     # 0: never pick the Winograd F(2x2,3x3) algorithm
 WGRAD_F34 = os.environ.get('Y2_WGRAD_F34', '1') != '0'     # offer the 4x4-tile Winograd weight gradient (F(3x3, 4x4)) to the per-layer measurement
-FORCE_ALGO = os.environ.get('Y2_FORCE_ALGO') or None     # 'direct' | 'winograd' | 'fused' | 'implicit' | 'fused3' | 'implicit3' | 'split': no autotune, that algorithm wherever the library accepts it
-if FORCE_ALGO not in (None, 'direct', 'winograd', 'fused', 'implicit', 'fused3', 'implicit3', 'split'):
-    raise ValueError('Y2_FORCE_ALGO must be direct, winograd, fused, implicit, fused3, implicit3 or split (got %r)' % FORCE_ALGO)      # ('split': the algorithm of the current split mode; '...3': the two-workgroups-per-CU kernel)
+# Y2_FORCE_ALGO: no autotune, the named algorithm wherever the library accepts it.  name -> (algo, tile); None: the direct kernel everywhere; 'split': the
+# algorithm of the current split mode (split_algo()); '...3': the two-workgroups-per-CU kernel
+FORCE_ALGOS = {'direct': None, 'winograd': (ALGO_WINOGRAD, 5), 'fused': (ALGO_WINOGRAD_FUSED, 0), 'implicit': (ALGO_WINOGRAD_IMPLICIT, 0),
+               'fused3': (ALGO_WINOGRAD_FUSED, 3), 'implicit3': (ALGO_WINOGRAD_IMPLICIT, 3), 'split': (ALGO_WINOGRAD_SPLIT, 0)}
+FORCE_ALGO = os.environ.get('Y2_FORCE_ALGO') or None
+if FORCE_ALGO is not None and FORCE_ALGO not in FORCE_ALGOS:
+    raise ValueError('Y2_FORCE_ALGO must be %s or %s (got %r)' % (', '.join(list(FORCE_ALGOS)[:-1]), list(FORCE_ALGOS)[-1], FORCE_ALGO))
 # Opt-in precision modes: the Winograd GEMMs may run on the bf16 / fp16 matrix pipe from split operands (csrc/gemm_split.hip): fp32-level
 # accuracy (the same parity tests run in these modes).  SPLIT = 'bf16' (True): three bf16 planes per fp32 operand, six plane products
 # (Y2_ALGO_WINOGRAD_SPLIT; fp32's exponent range); 'f16': two fp16 planes, three products, operands scaled by fixed powers of two
@@ -537,7 +555,7 @@ def split_overflowed(reset=True):
 
 
 def split_algo():
-    return 5 if split_mode() == 'f16' else 4
+    return ALGO_WINOGRAD_SPLIT_F16 if split_mode() == 'f16' else ALGO_WINOGRAD_SPLIT
 
 
 def split_planes(t, mode=None):
@@ -560,7 +578,7 @@ FORCE_GRAD = os.environ.get('Y2_FORCE_GRAD_ALGO') or None
 FORCE_WGRAD = os.environ.get('Y2_FORCE_WGRAD') or None
 if FORCE_GRAD not in (None, 'f43', 'direct') or FORCE_WGRAD not in (None, 'direct', 'wino', 'f34'):
     raise ValueError('Y2_FORCE_GRAD_ALGO must be f43 or direct, Y2_FORCE_WGRAD direct, wino or f34')
-PERSIST = os.environ.get('Y2_CONV_PERSIST', '1') != '0'      # 0: never offer the persistent-workgroup tiles (11 / 12 / 13 / 15) of the direct kernel (A/B runs)
+PERSIST = os.environ.get('Y2_CONV_PERSIST', '1') != '0'      # 0: never offer the persistent-workgroup tiles (PERSISTENT_TILES) of the direct kernel (A/B runs)
 IMPLICIT = os.environ.get('Y2_WINO_IMPLICIT', '1') != '0'  # 0: never offer Y2_ALGO_WINOGRAD_IMPLICIT (A/B runs)
 WINO_MIN_CIN = 32                                        # below this the transforms cost more than the GEMM saves (measured; 32: the 208x208 layer, one K slab per tile of the fused kernels)
 
@@ -584,13 +602,14 @@ def wino_weight(wp, cout, cin):
     return u
 
 
-def _time_conv(L, params, st):
+def _best_of(n, m, launch):
+    """Milliseconds of the fastest of n batches of m launches (HIP events on torch's current stream; several batches: DVFS / neighbour noise)."""
     t = float('inf')
-    for _ in range(3):          # best of three batches of 3 launches (DVFS / neighbour noise)
+    for _ in range(n):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(3):
-            L.y2_conv_fwd(ctypes.byref(params), st)
+        for _ in range(m):
+            launch()
         e1.record()
         e1.synchronize()
         t = min(t, e0.elapsed_time(e1))
@@ -602,137 +621,183 @@ class OperandMissing(RuntimeError):
     warm-up passes used: model.train_graph)."""
 
 
+# ---- autotune_conv, step by step.  What one problem is OFFERED: wino - the Winograd forms at all; split / implicit / f43 - Y2_ALGO_WINOGRAD_SPLIT(_F16),
+# _IMPLICIT, _F43.  may_implicit (the caller lets the transformed input stay unwritten, and Y2_WINO_IMPLICIT) and grad (the result is a gradient: `f43` was
+# given) are the caller's flags as the table key and the pinned-gradient rule read them.
+ConvOffer = collections.namedtuple('ConvOffer', 'wino split implicit f43 may_implicit grad')
+# The filter operands one call has at hand: packed weight (address), U, its split planes and their distance, U6 or a callable producing it - built at most
+# once, into u6_built, when an algorithm that reads it is applied
+ConvOperands = collections.namedtuple('ConvOperands', 'direct u split split_plane u6 u6_built')
+
+
+def conv_offer(params, wino_w, implicit_ok, wino_split, f43, wino_eligible):
+    # wino_eligible: the layer IS Winograd-eligible although `wino_w` is not at hand (None) - the problem keeps its identity (conv_key),
+    # and an algorithm that reads the missing operand raises OperandMissing instead of being silently replaced by another one
+    wino = bool(((wino_w is not None) if wino_eligible is None else bool(wino_eligible)) and WINOGRAD and params.ksize == 3 and params.stride in (0, 1)
+                and params.pad_plus1 in (0, 2) and not params.transposed and not params.residual and params.out_mode == 0)
+    may_implicit = bool(implicit_ok and IMPLICIT)
+    return ConvOffer(wino=wino, split=bool(wino and SPLIT and wino_split is not None and params.Cin % 32 == 0), implicit=may_implicit and params.Cin % 32 == 0,
+                     f43=bool(f43 is not None and wino and not DETERMINISTIC and params.y and not params.y_pool and not params.stats),
+                     may_implicit=may_implicit, grad=f43 is not None)
+
+
+def conv_key(params, dev, offer):
+    """The problem's key in the table of measured choices (_TUNE, tune/default_gfx950.json): every committed entry depends on it element for element."""
+    return (params.B, params.H, params.W, params.Cin, params.ldx, params.Cout, params.ksize, bool(params.y), bool(params.y_pool),
+            bool(params.stats), params.out_mode, params.stride, params.pad_plus1, bool(params.residual), params.transposed, params.out_h, params.out_w, str(dev),
+            offer.wino, offer.may_implicit) + (('split', split_mode()) if offer.split else ()) + (('f43',) if (offer.grad and offer.wino) else ())
+
+
+def _accepted(params):
+    return lib().y2_conv_fwd_workspace_bytes(ctypes.byref(params)) >= 0      # the library accepts this problem (sizes, alignment)
+
+
+def known_choice(params, dev, key, offer):
+    """The (algo, tile) this problem is KNOWN to take - pinned by Y2_FORCE_GRAD_ALGO, or in the table - else None."""
+    if FORCE_GRAD is not None and offer.grad:
+        # a data gradient under a pinned gradient algorithm.  The library is asked about a COPY with aligned dummies: a missing operand is no refusal
+        q = ConvParams.from_buffer_copy(params)
+        q.algo, q.tile, q.x, q.w, q.y = ALGO_WINOGRAD_F43, 5, q.x or 256, 256, q.y or 256
+        return (ALGO_WINOGRAD_F43, 5) if (FORCE_GRAD == 'f43' and offer.f43 and _accepted(q)) else (ALGO_DIRECT, 0)
+    if FORCE_ALGO is not None:
+        return None
+    if str(dev) not in _DEFAULTS_SEEN:
+        load_tune_defaults(dev)
+    hit = None if DETERMINISTIC else _TUNE.get(key)      # deterministic mode ignores measured choices (they may differ between runs)
+    hit = None if hit is None else (tuple(hit) if isinstance(hit, (list, tuple)) else (ALGO_DIRECT, hit))
+    # Y2_CONV_PERSIST=0 (A/B switch): a table entry that names a persistent tile does not count - measure (or fall back) without them
+    return hit if (hit is None or PERSIST or not (hit[0] == ALGO_DIRECT and hit[1] in PERSISTENT_TILES)) else None
+
+
+def forced_choice(params, offer):
+    """Y2_FORCE_ALGO - deterministic algorithm coverage (tests, A/B runs): every eligible layer takes the named algorithm, everything else the
+    direct kernel with the library's own tile choice; no measurement, no cache.  The list first_accepted tries (empty: the direct kernel)."""
+    want = FORCE_ALGOS[FORCE_ALGO]
+    if want is not None and want[0] in ALGOS_SPLIT:
+        want = (split_algo(), want[1])
+    if want is not None and want[0] == ALGO_WINOGRAD_IMPLICIT and not offer.implicit:
+        want = (ALGO_WINOGRAD_FUSED, want[1])         # where the transformed input must stay behind: the fused kernel that reads it
+    if want is not None and want[0] in ALGOS_SPLIT and not offer.split:
+        want = (ALGO_WINOGRAD, 5) if offer.wino else None
+    return [want] if (want is not None and offer.wino and (want[0] == ALGO_WINOGRAD or params.Cin % 32 == 0)) else []
+
+
+def static_preferences(params, offer):
+    """No measurement possible (Y2_AUTOTUNE=0, a graph capture) or wanted (deterministic mode: a timed choice may differ from run to run and with it the
+    rounding): the choices the measurements converge to on MI355X (profiles/r01_detect_b32_layer_table.txt), best first."""
+    hw, prefer = params.H * params.W, []
+    if offer.f43 and params.Cin >= 128 and hw <= 19 * 19:
+        prefer.append((ALGO_WINOGRAD_F43, 5))      # gradients of the 13x13 (19x19) layers: 4x4 tiles, 64x128 GEMM tiles
+    if offer.split and hw <= 19 * 19:
+        prefer.append((split_algo(), 0))           # opt-in split mode: the 13x13 (19x19 at 608) layers, 25-30 % ahead of the fp32 GEMMs there
+    if offer.wino and offer.implicit and (hw >= 52 * 52 or (hw >= 26 * 26 and params.Cout <= params.Cin)):
+        if params.Cin <= 128:
+            prefer.append((ALGO_WINOGRAD_IMPLICIT, 3))   # ... its two-workgroups-per-CU form where the K loop is short (11-13 % ahead on the 104x104 / 52x52 layers)
+        prefer.append((ALGO_WINOGRAD_IMPLICIT, 0))       # fused Winograd with the input transform in its loader: the large maps and the data gradients
+    if offer.wino and params.Cin % 32 == 0 and hw >= 26 * 26:
+        prefer.append((ALGO_WINOGRAD_FUSED, 0))          # fused Winograd on the 104x104 ... 26x26 layers
+    if offer.wino and params.Cin >= 128:
+        prefer.append((ALGO_WINOGRAD, 5))                # three-kernel Winograd, 64x128 GEMM tiles, on the 13x13 layers
+    return prefer
+
+
+def conv_candidates(params, offer):
+    """What a measurement times, in this order (a tie goes to the earlier one)."""
+    big = params.B * params.H * params.W >= 65536 and params.Cout >= 128 and params.ksize in (1, 3) and params.stride in (0, 1) \
+        and params.pad_plus1 in (0, (params.ksize - 1) // 2 + 1) and not params.transposed and not params.residual
+    cands = [(ALGO_DIRECT, t) for t in [5, 3, 2, 1] + ([6] if params.Cout <= 32 else []) + ([8, 9] if big else [])]      # 8, 9: 512-thread 256x128 / 128x256 tiles
+    if PERSIST and params.ksize == 1 and params.stride in (0, 1) and params.pad_plus1 in (0, 1) and not params.transposed and not params.y_pool and params.Cin % 32 == 0:
+        cands += [(ALGO_DIRECT, t) for t in (15, 13, 12, 11)]      # 1x1 layers (short K loops): persistent workgroups, next tile's first slab fetched under the current tile's last
+    if offer.wino:
+        cands += [(ALGO_WINOGRAD, t) for t in (5, 3, 2, 1)]
+        if params.Cin % 32 == 0:
+            cands.append((ALGO_WINOGRAD_FUSED, 0))        # fused GEMM + output transform (no product tensor): pays on the 52x52 layers
+        if offer.implicit:
+            cands.append((ALGO_WINOGRAD_IMPLICIT, 0))     # ... with the input transform in its loader (no transformed input in memory either)
+        if params.Cin % 32 == 0:
+            cands.append((ALGO_WINOGRAD_FUSED, 3))        # the same two as 32 x 64 units, two workgroups per CU (wino_fused3_kernel): short K loops, small grids
+            if offer.implicit:
+                cands.append((ALGO_WINOGRAD_IMPLICIT, 3))
+        if offer.split:
+            cands.append((split_algo(), 0))               # three-kernel Winograd with the GEMMs on the bf16 / fp16 pipe (opt-in precision modes)
+        if offer.f43:
+            cands += [(ALGO_WINOGRAD_F43, t) for t in (5, 3, 2, 1)]      # gradients: Winograd F(4x4,3x3), three kernels, 36 GEMMs
+    return cands
+
+
+def apply_choice(params, ops, choice):
+    """Write algo / tile and the filter operand that algorithm reads into params; OperandMissing when the caller has not prepared it."""
+    algo, tile = choice
+    if algo in ALGOS_READ_U and ops.u is None:
+        raise OperandMissing('algorithm %d reads the Winograd filter transform, which the caller did not prepare' % algo)
+    params.algo, params.tile = algo, tile
+    if algo == ALGO_WINOGRAD_F43 and not ops.u6_built:
+        ops.u6_built.append(ops.u6() if callable(ops.u6) else ops.u6)
+    params.w = ops.split.data_ptr() if algo in ALGOS_SPLIT else ops.u.data_ptr() if algo in ALGOS_READ_U else ops.u6_built[0].data_ptr() if algo == ALGO_WINOGRAD_F43 else ops.direct
+    params.w_plane = ops.split_plane if algo in ALGOS_SPLIT else 0
+    # the 4x4-tile filter operand exists only here: it must outlive this function (the caller launches with params AFTER it returns, and a
+    # workspace that grows in between would be handed the freed block): the tensor rides on the params object
+    params._f43_operand = ops.u6_built if algo == ALGO_WINOGRAD_F43 else None
+    return choice
+
+
+def first_accepted(params, ops, choices):
+    """Apply the first of `choices` the library accepts; none: the direct kernel with the library's own tile choice."""
+    for c in choices:
+        apply_choice(params, ops, c)
+        if _accepted(params):
+            return c
+    return apply_choice(params, ops, (ALGO_DIRECT, 0))
+
+
+def measure_conv(params, dev, ops, cands):
+    """Time every candidate the library accepts and launches (1 launch, then the best of 3 batches of 3); the outputs written are real outputs."""
+    L, st = lib(), stream()
+    best, best_t = (ALGO_DIRECT, 0), float('inf')
+    stats_save = params.stats
+    params.stats = None          # timing launches must not accumulate statistics twice
+    for choice in cands:
+        apply_choice(params, ops, choice)
+        if conv_workspace(params, dev) < 0:
+            continue
+        if L.y2_conv_fwd(ctypes.byref(params), st) != 0:
+            continue
+        t = _best_of(3, 3, lambda: L.y2_conv_fwd(ctypes.byref(params), st))
+        if t < best_t:
+            best, best_t = choice, t
+    params.stats = stats_save
+    return best
+
+
 def autotune_conv(params, dev, wino_w=None, implicit_ok=True, wino_split=None, split_plane=0, f43=None, wino_eligible=None, peek=False, choice=None):
     """Measure-don't-guess algorithm + tile selection for one y2_conv_fwd problem: the first time a problem shape is seen,
     every tile configuration of the direct kernel - and, when `wino_w` (y2_wino_weight output) is given, of the Winograd
-    path - is timed (HIP events, best of 2 x 3 launches) and the fastest is cached for the process; later calls only
+    path - is timed (HIP events, best of 3 x 3 launches) and the fastest is cached for the process; later calls only
     look the answer up.  Sets params.algo / params.tile / params.w.  The outputs written while timing are real outputs.
     Never measures while a hipGraph is being captured (plans are built during warm-up).
     implicit_ok=False: the caller wants the transformed input left in the workspace (training keeps it for the weight gradient),
-    so the algorithm that never materialises it (3) is not offered.
+    so the algorithm that never materialises it (Y2_ALGO_WINOGRAD_IMPLICIT) is not offered.
     f43: the result is a GRADIENT and may take Winograd F(4x4,3x3) (Y2_ALGO_WINOGRAD_F43, 8-9e-6 x rms per layer): the y2_wino6_weight operand
     or a callable producing it (called only when that algorithm is timed or chosen).
     peek=True: the (algo, tile) this problem is KNOWN to take - pinned by Y2_FORCE_GRAD_ALGO, or in the table - else None (Y2_FORCE_ALGO, the
     deterministic mode, the static preferences): nothing is measured, allocated or written to params (its pointers may be dummies).  A call without
     peek is that lookup, then measure-if-unknown, then apply.  choice=(algo, tile): a decision taken earlier is applied (operand checks, lifetime rule), not looked up."""
-    # wino_eligible: the layer IS Winograd-eligible although `wino_w` is not at hand (None) - the problem keeps its identity (the key below),
-    # and an algorithm that reads the missing operand raises OperandMissing instead of being silently replaced by another one
-    wino_ok = (((wino_w is not None) if wino_eligible is None else bool(wino_eligible)) and WINOGRAD and params.ksize == 3 and params.stride in (0, 1)
-               and params.pad_plus1 in (0, 2) and not params.transposed and not params.residual and params.out_mode == 0)
-    split_ok = bool(wino_ok and SPLIT and wino_split is not None and params.Cin % 32 == 0)
-    key = (params.B, params.H, params.W, params.Cin, params.ldx, params.Cout, params.ksize, bool(params.y), bool(params.y_pool),
-           bool(params.stats), params.out_mode, params.stride, params.pad_plus1, bool(params.residual), params.transposed, params.out_h, params.out_w, str(dev),
-           bool(wino_ok), bool(implicit_ok and IMPLICIT)) + (('split', split_mode()) if split_ok else ()) + (('f43',) if (f43 is not None and wino_ok) else ())
-    f43_ok = f43 is not None and wino_ok and not DETERMINISTIC and params.y and not params.y_pool and not params.stats
-    f43_t = []
-
-    def f43_w():
-        if not f43_t:
-            f43_t.append(f43() if callable(f43) else f43)
-        return f43_t[0]
-    implicit_ok = bool(implicit_ok and IMPLICIT) and params.Cin % 32 == 0
-    w_direct = params.w
-
-    def apply(choice):
-        algo, tile = choice
-        if algo in (1, 2, 3) and wino_w is None:
-            raise OperandMissing('algorithm %d reads the Winograd filter transform, which the caller did not prepare' % algo)
-        params.algo, params.tile = algo, tile
-        params.w = wino_split.data_ptr() if algo in (4, 5) else wino_w.data_ptr() if algo in (1, 2, 3) else f43_w().data_ptr() if algo == 6 else w_direct
-        params.w_plane = split_plane if algo in (4, 5) else 0
-        # the 4x4-tile filter operand exists only here: it must outlive this function (the caller launches with params AFTER it returns, and a
-        # workspace that grows in between would be handed the freed block): the tensor rides on the params object
-        params._f43_operand = f43_t if algo == 6 else None
-        return choice
-
-    def first_accepted(cands):
-        for c in cands:
-            apply(c)
-            if lib().y2_conv_fwd_workspace_bytes(ctypes.byref(params)) >= 0:      # the library accepts this problem (sizes, alignment)
-                return c
-        return apply((0, 0))
-
-    def known():
-        if FORCE_GRAD is not None and f43 is not None:
-            # a data gradient under a pinned gradient algorithm.  The library is asked about a COPY with aligned dummies: a missing operand is no refusal
-            q = ConvParams.from_buffer_copy(params)
-            q.algo, q.tile, q.x, q.w, q.y = 6, 5, q.x or 256, 256, q.y or 256
-            return (6, 5) if (FORCE_GRAD == 'f43' and f43_ok and lib().y2_conv_fwd_workspace_bytes(ctypes.byref(q)) >= 0) else (0, 0)
-        if FORCE_ALGO is not None:
-            return None
-        if str(dev) not in _DEFAULTS_SEEN:
-            load_tune_defaults(dev)
-        hit = None if DETERMINISTIC else _TUNE.get(key)      # deterministic mode ignores measured choices (they may differ between runs)
-        hit = None if hit is None else (tuple(hit) if isinstance(hit, (list, tuple)) else (0, hit))
-        # Y2_CONV_PERSIST=0 (A/B switch): a table entry that names a persistent tile does not count - measure (or fall back) without them
-        return hit if (hit is None or PERSIST or not (hit[0] == 0 and hit[1] in (11, 12, 13, 15))) else None
+    offer = conv_offer(params, wino_w, implicit_ok, wino_split, f43, wino_eligible)
+    key = conv_key(params, dev, offer)
+    ops = ConvOperands(direct=params.w, u=wino_w, split=wino_split, split_plane=split_plane, u6=f43, u6_built=[])
     if choice is None:
-        choice = known()
+        choice = known_choice(params, dev, key, offer)
     if peek:
         return choice
     if choice is not None:
-        return apply(tuple(choice))
+        return apply_choice(params, ops, tuple(choice))
     if FORCE_ALGO is not None:
-        # deterministic algorithm coverage (tests, A/B runs): every eligible layer takes the named algorithm, everything else the
-        # direct kernel with the library's own tile choice; no measurement, no cache
-        want = {'direct': None, 'winograd': (1, 5), 'fused': (2, 0), 'implicit': (3, 0), 'fused3': (2, 3), 'implicit3': (3, 3), 'split': (split_algo(), 0)}[FORCE_ALGO]
-        if want is not None and want[0] == 3 and not implicit_ok:
-            want = (2, want[1])         # where the transformed input must stay behind: the fused kernel that reads it
-        if want is not None and want[0] in (4, 5) and not split_ok:
-            want = (1, 5) if wino_ok else None
-        return first_accepted([want] if (want is not None and wino_ok and (want[0] == 1 or params.Cin % 32 == 0)) else [])
+        return first_accepted(params, ops, forced_choice(params, offer))
     if not AUTOTUNE or DETERMINISTIC or torch.cuda.is_current_stream_capturing():
-        # no measurement possible (or, deterministic mode: a timed choice may differ from run to run and with it the rounding): the choices the measurements converge to on MI355X (profiles/r01_detect_b32_layer_table.txt)
-        prefer = []
-        if f43_ok and params.Cin >= 128 and params.H * params.W <= 19 * 19:
-            prefer.append((6, 5))                  # gradients of the 13x13 (19x19) layers: 4x4 tiles, 64x128 GEMM tiles
-        if split_ok and params.H * params.W <= 19 * 19:
-            prefer.append((split_algo(), 0))       # opt-in split mode: the 13x13 (19x19 at 608) layers, 25-30 % ahead of the fp32 GEMMs there
-        if wino_ok and implicit_ok and (params.H * params.W >= 52 * 52 or (params.H * params.W >= 26 * 26 and params.Cout <= params.Cin)):
-            if params.Cin <= 128:
-                prefer.append((3, 3))   # ... its two-workgroups-per-CU form where the K loop is short (11-13 % ahead on the 104x104 / 52x52 layers)
-            prefer.append((3, 0))       # fused Winograd with the input transform in its loader: the large maps and the data gradients
-        if wino_ok and params.Cin % 32 == 0 and params.H * params.W >= 26 * 26:
-            prefer.append((2, 0))       # fused Winograd on the 104x104 ... 26x26 layers
-        if wino_ok and params.Cin >= 128:
-            prefer.append((1, 5))       # three-kernel Winograd, 64x128 GEMM tiles, on the 13x13 layers
-        return first_accepted(prefer)
-    L = lib()
-    st = stream()
-    big = params.B * params.H * params.W >= 65536 and params.Cout >= 128 and params.ksize in (1, 3) and params.stride in (0, 1) \
-        and params.pad_plus1 in (0, (params.ksize - 1) // 2 + 1) and not params.transposed and not params.residual
-    cands = [(0, t) for t in [5, 3, 2, 1] + ([6] if params.Cout <= 32 else []) + ([8, 9] if big else [])]      # 8, 9: 512-thread 256x128 / 128x256 tiles
-    if PERSIST and params.ksize == 1 and params.stride in (0, 1) and params.pad_plus1 in (0, 1) and not params.transposed and not params.y_pool and params.Cin % 32 == 0:
-        cands += [(0, t) for t in (15, 13, 12, 11)]      # 1x1 layers (short K loops): persistent workgroups, next tile's first slab fetched under the current tile's last
-    if wino_ok:
-        cands += [(1, t) for t in (5, 3, 2, 1)]
-        if params.Cin % 32 == 0:
-            cands.append((2, 0))        # fused GEMM + output transform (no product tensor): pays on the 52x52 layers
-        if implicit_ok:
-            cands.append((3, 0))        # ... with the input transform in its loader (no transformed input in memory either)
-        if params.Cin % 32 == 0:
-            cands.append((2, 3))        # the same two as 32 x 64 units, two workgroups per CU (wino_fused3_kernel): short K loops, small grids
-            if implicit_ok:
-                cands.append((3, 3))
-        if split_ok:
-            cands.append((split_algo(), 0))        # three-kernel Winograd with the GEMMs on the bf16 / fp16 pipe (opt-in precision modes)
-        if f43_ok:
-            cands += [(6, t) for t in (5, 3, 2, 1)]      # gradients: Winograd F(4x4,3x3), three kernels, 36 GEMMs
-    best, best_t = (0, 0), float('inf')
-    stats_save = params.stats
-    params.stats = None          # timing launches must not accumulate statistics twice
-    for choice in cands:
-        apply(choice)
-        if conv_workspace(params, dev) < 0:
-            continue
-        if L.y2_conv_fwd(ctypes.byref(params), st) != 0:
-            continue
-        t = _time_conv(L, params, st)
-        if t < best_t:
-            best, best_t = choice, t
-    params.stats = stats_save
+        return first_accepted(params, ops, static_preferences(params, offer))
+    best = measure_conv(params, dev, ops, conv_candidates(params, offer))
     tune_store(key, list(best))       # a problem shape neither this process nor the committed table had met (TUNE_MISSES: bench.py reports the count per leg)
-    return apply(best)
+    return apply_choice(params, ops, best)
 
 
 def tune_lookup(key, dev):
@@ -796,20 +861,35 @@ _WGRAD_WS = {}
 
 
 def wgrad_choice(B, H, W, cin, ldx, cout, ldz, k, has_v, dev):
-    """Which kernel conv_wgrad will run for this problem: 0 = y2_conv_wgrad (accumulates into a ZEROED buffer), 1 = y2_wino_wgrad
-    (2x2 gradient tiles; overwrites), 2 = its 4x4-tile form (Winograd F(3x3, 4x4): fewer multiply-adds, never reads the forward's
+    """Which kernel conv_wgrad will run for this problem: WGRAD_DIRECT (0) = y2_conv_wgrad (accumulates into a ZEROED buffer), WGRAD_WINO (1) = y2_wino_wgrad
+    (2x2 gradient tiles; overwrites), WGRAD_WINO_F34 (2) = its 4x4-tile form (Winograd F(3x3, 4x4): fewer multiply-adds, never reads the forward's
     transformed input; overwrites), None = eligible for all and not measured yet (conv_wgrad will time them and zero the buffer itself)."""
     if not eligible_wino(cout, cin, k, ldx, ldz):
-        return 0
+        return WGRAD_DIRECT
     if FORCE_WGRAD is not None and not DETERMINISTIC:
-        return {'direct': 0, 'wino': 1, 'f34': 2}[FORCE_WGRAD]
+        return {'direct': WGRAD_DIRECT, 'wino': WGRAD_WINO, 'f34': WGRAD_WINO_F34}[FORCE_WGRAD]
     if DETERMINISTIC or not AUTOTUNE:
-        if not DETERMINISTIC and WGRAD_F34 and cin >= 128 and H * W <= 19 * 19:
-            return 2                    # what the measurements converge to on the 13x13 (19x19) layers
-        return 1 if cin >= 128 else 0
+        return _wgrad_static(cin, H, W)
     if str(dev) not in _DEFAULTS_SEEN:
         load_tune_defaults(dev)
-    return _TUNE.get(('wgrad', B, H, W, cin, ldx, cout, ldz, bool(has_v), str(dev)))
+    return _TUNE.get(wgrad_key(B, H, W, cin, ldx, cout, ldz, has_v, dev))
+
+
+def wgrad_key(B, H, W, cin, ldx, cout, ldz, has_v, dev):
+    return ('wgrad', B, H, W, cin, ldx, cout, ldz, bool(has_v), str(dev))
+
+
+def _wgrad_static(cin, H, W):
+    """No measurement wanted (Y2_AUTOTUNE=0, deterministic mode): what the measurements converge to."""
+    if not DETERMINISTIC and WGRAD_F34 and cin >= 128 and H * W <= 19 * 19:
+        return WGRAD_WINO_F34               # the 13x13 (19x19) layers; the library refuses this form in deterministic mode
+    return WGRAD_WINO if cin >= 128 else WGRAD_DIRECT
+
+
+def _wgrad_capturing(cin):
+    """An unmeasured problem met while a graph is captured.  _wgrad_static without its 4x4-tile clause, on purpose: this answer is not recorded and the
+    caller has planned for the unknown (dz materialised, nothing fused): the 4x4-tile form is taken only where a measurement, the table or a pin names it."""
+    return WGRAD_WINO if cin >= 128 else WGRAD_DIRECT
 
 
 def _wgrad_scratch(dev, need):
@@ -839,74 +919,67 @@ def conv_wgrad(x, dz, B, H, W, cin, ldx, cout, ldz, k, v=None, out=None, zeroed=
     floats) instead of a fresh tensor; `zeroed`: the caller has zero-filled it (one y2_multi launch for all layers of a step).
     `native`: a [cout][cin][3][3] destination; when the choice is the Winograd reduction it is written directly in that layout and
     returned INSTEAD of the packed buffer (the caller checks `result is native`).
-    `choice`: what wgrad_choice answered when the caller planned this launch (0, 1, 2): exactly that kernel runs, the table is not read again.
+    `choice`: what wgrad_choice answered when the caller planned this launch (WGRAD_DIRECT / _WINO / _WINO_F34): exactly that kernel runs, the table is not read again.
     None (not given, or unmeasured then): looked up here, measured when unknown and not capturing.  Fills and launches go to the launch stream."""
     L, st, dev = lib(), stream(), x.device
     nw = cout * cin * k * k
     eligible = eligible_wino(cout, cin, k, ldx, ldz)
     if choice is None:
         choice = wgrad_choice(B, H, W, cin, ldx, cout, ldz, k, v is not None, dev)
-    assert choice in (None, 0) or eligible
+    assert choice in (None, WGRAD_DIRECT) or eligible
 
-    def wino_ex(dst, ld, mode, vt=None):          # scratch modes: 6 serves both forms that read a transformed gradient (6 packed, 7 native)
-        ws = _wgrad_scratch(dev, L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, min(mode, 6)))
+    def wino_ex(dst, ld, mode, vt=None):          # (one scratch size serves both forms that read a transformed gradient)
+        ws = _wgrad_scratch(dev, L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, WINO_WGRAD_F34_PRE if mode == WINO_WGRAD_F34_PRE_NATIVE else mode))
         check(L.y2_wino_wgrad_ex(ptr(x), ptr(dz), ptr(dst), B, H, W, cin, ldx, cout, ld, ptr(vt), ptr(ws), ws.numel() * 4, mode, st), 'y2_wino_wgrad_ex')
         return dst
     if dz_pre:
         # `dz` is the transformed gradient [36][T][cout] of the 4x4-tile form (y2_bn_act_bwd_wino6), built by a caller that had decided on that form
-        assert choice == 2, choice
+        assert choice == WGRAD_WINO_F34, choice
         if native is not None:
-            return wino_ex(native, cout, 7)
-        return wino_ex(out if out is not None else torch.empty(nw, dtype=torch.float32, device=dev), cout, 6)
+            return wino_ex(native, cout, WINO_WGRAD_F34_PRE_NATIVE)
+        return wino_ex(out if out is not None else torch.empty(nw, dtype=torch.float32, device=dev), cout, WINO_WGRAD_F34_PRE)
     # the direct kernel accumulates split partial sums into a zeroed buffer; the Winograd path overwrites (no fill needed)
-    if native is not None and choice in (1, 2):
+    if native is not None and choice in (WGRAD_WINO, WGRAD_WINO_F34):
         assert native.numel() == nw and native.is_contiguous()
-        return wino_ex(native, ldz, 1 if choice == 1 else 3, v if choice == 1 else None)
+        return wino_ex(native, ldz, WINO_WGRAD_NATIVE, v) if choice == WGRAD_WINO else wino_ex(native, ldz, WINO_WGRAD_F34_NATIVE)
     dwp = out if out is not None else torch.empty(nw, dtype=torch.float32, device=dev)
     assert dwp.numel() >= nw and dwp.is_contiguous()
-    if choice not in (1, 2) and not zeroed:
+    if choice not in (WGRAD_WINO, WGRAD_WINO_F34) and not zeroed:
         multi([(MULTI_ZERO, dwp, None)], st)
 
     def direct():
         check(L.y2_conv_wgrad(ptr(x), ptr(dz), ptr(dwp), B, H, W, cin, ldx, cout, ldz, k, st), 'y2_conv_wgrad')
     ws = None
-    if choice != 0:      # (a layer whose measured choice is the direct kernel needs no Winograd scratch: the 208x208 layer alone would size it at 4-9 GB)
-        need = L.y2_wino_wgrad_workspace_bytes(B, H, W, cin, cout) if choice is None else L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, 2 if choice == 2 else 0)
+    if choice != WGRAD_DIRECT:      # (a layer whose measured choice is the direct kernel needs no Winograd scratch: the 208x208 layer alone would size it at 4-9 GB)
+        need = L.y2_wino_wgrad_workspace_bytes(B, H, W, cin, cout) if choice is None else \
+            L.y2_wino_wgrad_workspace_bytes_ex(B, H, W, cin, cout, WINO_WGRAD_F34 if choice == WGRAD_WINO_F34 else WINO_WGRAD_PACKED)
         ws = _wgrad_scratch(dev, need)
 
     def wino():
         check(L.y2_wino_wgrad(ptr(x), ptr(dz), ptr(dwp), B, H, W, cin, ldx, cout, ldz, ptr(v), ptr(ws), ws.numel() * 4, st), 'y2_wino_wgrad')
-    def wino6():
-        check(L.y2_wino_wgrad_ex(ptr(x), ptr(dz), ptr(dwp), B, H, W, cin, ldx, cout, ldz, None, ptr(ws), ws.numel() * 4, 2, st), 'y2_wino_wgrad_ex')
-    if choice is None:
-        if torch.cuda.is_current_stream_capturing():
-            choice = 1 if cin >= 128 else 0
-        else:
-            times = []
-            for fn in (direct, wino) + ((wino6,) if WGRAD_F34 else ()):
-                with _timing_stream():
-                    fn()
-                    t = float('inf')
-                    for _ in range(2):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        fn()
-                        fn()
-                        e1.record()
-                        e1.synchronize()
-                        t = min(t, e0.elapsed_time(e1))
-                times.append(t)
-            if v is not None and H * W >= 52 * 52 and len(times) > 1:
-                # The 2x2-tile reduction reads the forward's transformed input V: choosing it makes the FORWARD of this layer keep V, i.e. run
-                # the input-transform kernel (|x| read + 4|x| written at ~5.5 TB/s) in front of a V-reading algorithm instead of the implicit
-                # one the large maps otherwise take.  That cost belongs to this choice (round 5: on the 208x208 layer the reduction measured
-                # 0.93 ms against 0.98 ms for the direct kernel and made the forward 0.32 ms slower - the per-kernel comparison cannot see it;
-                # on the 104x104 layers it wins even so).  times are for two launches.
-                times[1] += 2.0 * 5.0 * B * H * W * cin * 4 / 5.5e9
-            choice = times.index(min(times))
-            tune_store(('wgrad', B, H, W, cin, ldx, cout, ldz, v is not None, str(dev)), choice)
-            multi([(MULTI_ZERO, dwp, None)], st)          # the timing launches of the direct kernel accumulated into dwp
-    (direct, wino, wino6)[choice]()
+
+    def wino_f34():
+        check(L.y2_wino_wgrad_ex(ptr(x), ptr(dz), ptr(dwp), B, H, W, cin, ldx, cout, ldz, None, ptr(ws), ws.numel() * 4, WINO_WGRAD_F34, st), 'y2_wino_wgrad_ex')
+    kernels = (direct, wino, wino_f34)          # indexed by WGRAD_DIRECT, WGRAD_WINO, WGRAD_WINO_F34
+    if choice is None and torch.cuda.is_current_stream_capturing():
+        choice = _wgrad_capturing(cin)
+    elif choice is None:
+        times = []
+        for fn in kernels if WGRAD_F34 else kernels[:2]:
+            with _timing_stream():
+                fn()
+                times.append(_best_of(2, 2, fn))
+        if v is not None and H * W >= 52 * 52 and len(times) > 1:
+            # The 2x2-tile reduction reads the forward's transformed input V: choosing it makes the FORWARD of this layer keep V, i.e. run
+            # the input-transform kernel (|x| read + 4|x| written at ~5.5 TB/s) in front of a V-reading algorithm instead of the implicit
+            # one the large maps otherwise take.  That cost belongs to this choice (round 5: on the 208x208 layer the reduction measured
+            # 0.93 ms against 0.98 ms for the direct kernel and made the forward 0.32 ms slower - the per-kernel comparison cannot see it;
+            # on the 104x104 layers it wins even so).  times are for two launches.
+            times[WGRAD_WINO] += 2.0 * 5.0 * B * H * W * cin * 4 / 5.5e9
+        choice = times.index(min(times))
+        tune_store(wgrad_key(B, H, W, cin, ldx, cout, ldz, v is not None, dev), choice)
+        multi([(MULTI_ZERO, dwp, None)], st)          # the timing launches of the direct kernel accumulated into dwp
+    kernels[choice]()
     return dwp
 
 

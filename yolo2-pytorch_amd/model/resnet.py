@@ -149,7 +149,7 @@ class ResNet(parts.InferMixin, nn.Module):
             if plan['prep'] is not prep:
                 for p, conv in zip([plan['stem']] + list(plan['arr']), plan['convs']):
                     wp, scale, shift = prep[conv][:3]
-                    parts.PlanBuilder.rebind(p, prep['wino'].get(id(wp)) if p.algo in (1, 2, 3) else wp, scale, shift)
+                    parts.PlanBuilder.rebind(p, prep['wino'].get(id(wp)) if p.algo in _hip.ALGOS_READ_U else wp, scale, shift)
                 plan['prep'] = prep
             return plan
         build = parts.PlanBuilder(dev)

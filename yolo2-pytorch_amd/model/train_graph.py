@@ -126,14 +126,14 @@ def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=No
     _hip.autotune_conv(p, dev, wino_w=u, implicit_ok=not keep_v, wino_split=us if u is not None else None, split_plane=us_plane,
                        f43=f43_operand if (grad and _f43_offered(eligible, cin, H, W)) else None, wino_eligible=eligible, choice=choice)
     if pre is not None:
-        assert p.algo == 6, p.algo
-        p.algo, p.x, p.ldx = 7, pre.data_ptr(), cin          # Y2_ALGO_WINOGRAD_F43_PRE
-    if wp is None and (p.algo == 0 or (p.algo in (6, 7) and u6 is None)):
+        assert p.algo == _hip.ALGO_WINOGRAD_F43, p.algo
+        p.algo, p.x, p.ldx = _hip.ALGO_WINOGRAD_F43_PRE, pre.data_ptr(), cin
+    if wp is None and (p.algo == _hip.ALGO_DIRECT or (p.algo in _hip.ALGOS_READ_U6 and u6 is None)):
         raise OperandPruned('algorithm %d reads the packed weight, which this step did not prepare' % p.algo)
     if note is not None:
-        note('w' if p.algo == 0 else '6' if p.algo in (6, 7) else 'u')
+        note('w' if p.algo == _hip.ALGO_DIRECT else '6' if p.algo in _hip.ALGOS_READ_U6 else 'u')
     kept = None
-    if keep_v and p.algo in (1, 2):
+    if keep_v and p.algo in (_hip.ALGO_WINOGRAD, _hip.ALGO_WINOGRAD_FUSED):
         T = B * ((H + 1) // 2) * ((W + 1) // 2)
         if 16 * T * (cin + cout) * 4 <= _WINO_CHUNK_BYTES and 16 * T * cin * 4 < 0x7fffffff:        # one batch chunk: V covers the whole batch
             need = L.y2_conv_fwd_workspace_bytes(ctypes.byref(p))
@@ -364,8 +364,8 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
         if k != 3:
             return False
         with_v, without_v = (_hip.wgrad_choice(B, h, w, cin, ldx, cout, cout, k, hv, dev) for hv in (True, False))
-        # (0 = direct kernel, 2 = the 4x4-tile Winograd form: neither reads V; never had V and one of them won anyway: stays that way)
-        return not (with_v in (0, 2) or (with_v is None and without_v in (0, 2)))
+        no_v = (_hip.WGRAD_DIRECT, _hip.WGRAD_WINO_F34)          # neither reads V; never had V and one of them won anyway: stays that way
+        return not (with_v in no_v or (with_v is None and without_v in no_v))
 
     def run_block(name, mod, xin, ldx, h, w, pool, out_full=None, out_ld=0, out_off=0, out_mode=0, want_full=True, first=False):
         """raw conv + stats -> finalize -> act.  Returns (_Block, full activation or None, pooled activation or None)."""
@@ -512,10 +512,10 @@ def _decide_bwd(geo, B, dev, need_dx=False):
     """Every decision of one backward pass that something else in the pass depends on, taken ONCE, before the first launch, from the algorithm
     table as it is now: one _Plan per block.  No GPU call, no allocation; the records are values - a table that changes while the pass runs (a
     measurement in an earlier layer of the same shape, import_tune from the data-parallel wrapper) shows in the NEXT pass.
-    wgrad: _hip.wgrad_choice (0, 1, 2), None = unknown: it resolves at its launch (measured there), and what is prepared for it is right for any
+    wgrad: _hip.wgrad_choice (_hip.WGRAD_*), None = unknown: it resolves at its launch (measured there), and what is prepared for it is right for any
     outcome - dz is materialised, nothing is fused, the target is zero filled on the weight gradient's stream; zero: the target is in the step's one
     zero fill; final: the target IS the gradient tensor (no unpack pass); fuse0: the first layer forms dz inside its weight gradient - no dz tensor
-    (1.4 GB at batch 64), no second pass; fused6: the (6, tile) data-gradient choice of a block that takes y2_bn_act_bwd_wino6, else None; sel: pass 1 of the
+    (1.4 GB at batch 64), no second pass; fused6: the (ALGO_WINOGRAD_F43, tile) data-gradient choice of a block that takes y2_bn_act_bwd_wino6, else None; sel: pass 1 of the
     BatchNorm backward reads the block's z_sel (y2_bn_act_bwd_sel): its only gradient is the pooled one."""
     plans = []
     for g in geo:
@@ -525,17 +525,17 @@ def _decide_bwd(geo, B, dev, need_dx=False):
             small = g.cin <= 3 and g.cout <= 64          # y2_conv0_wgrad: writes the gradient's own layout, accumulating
             # (model/yolo2.py:78-79: conv + pool, nothing below it needs a data gradient: only the weight gradient reads dz - from (z, dy_pool) and the pass-1 sums)
             fuse0 = bool(FUSE_CONV0 and small and g.full is None and g.pooled and not (g.H & 1) and not (g.W & 15) and B * g.H * g.W * g.cout * 4 < 0xffff0000 and not need_dx)
-            plans.append(_Plan(0, small, small, fuse0, None, None, sel))
+            plans.append(_Plan(_hip.WGRAD_DIRECT, small, small, fuse0, None, None, sel))
             continue
         wgrad = _hip.wgrad_choice(B, g.H, g.W, g.cin, g.ldx, cop, cop, g.k, g.has_v, dev)
         # weight AND data gradient KNOWN to run the 4x4-tile forms: y2_bn_act_bwd_wino6 writes their two transforms instead of dz
         fused6 = problem = None
-        if (FUSE_WINO6 and wgrad == 2 and g.k == 3 and g.ud_ok is not None and not g.pooled and g.full == 0 and cop == g.cout and not g.padded
+        if (FUSE_WINO6 and wgrad == _hip.WGRAD_WINO_F34 and g.k == 3 and g.ud_ok is not None and not g.pooled and g.full == 0 and cop == g.cout and not g.padded
                 and DEBUG_TAP is None and not _hip.DETERMINISTIC and not _hip.split_mode()):
             problem = _problem(B, g.H, g.W, cop, cop, g.cin, g.k, g.cin)          # described once: the launch fills in its pointers
             hit = _hip.autotune_conv(problem, dev, f43=True if _f43_offered(g.ud_ok, cop, g.H, g.W) else None, wino_eligible=g.ud_ok, peek=True)
-            fused6 = tuple(hit) if (hit is not None and hit[0] == 6) else None
-        plans.append(_Plan(wgrad, wgrad == 0, g.k == 1 and cop == g.cout and not g.padded, False, fused6, problem if fused6 else None, sel))      # (final: [cout][1][cin] IS the state_dict layout)
+            fused6 = tuple(hit) if (hit is not None and hit[0] == _hip.ALGO_WINOGRAD_F43) else None
+        plans.append(_Plan(wgrad, wgrad == _hip.WGRAD_DIRECT, g.k == 1 and cop == g.cout and not g.padded, False, fused6, problem if fused6 else None, sel))      # (final: [cout][1][cin] IS the state_dict layout)
     return plans
 
 

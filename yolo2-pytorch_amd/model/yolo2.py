@@ -198,7 +198,7 @@ class Darknet(parts.InferMixin, nn.Module):
             if plan['prep'] is not prep:      # a training step ran in between
                 for p, blk in zip(plan['arr'], plan['blks']):
                     wp, scale, shift, u = prep[blk]
-                    parts.PlanBuilder.rebind(p, prep['split'][blk] if p.algo in (4, 5) else u if p.algo in (1, 2, 3) else wp, scale, shift)
+                    parts.PlanBuilder.rebind(p, prep['split'][blk] if p.algo in _hip.ALGOS_SPLIT else u if p.algo in _hip.ALGOS_READ_U else wp, scale, shift)
                 plan['prep'] = prep
             return plan
         build = parts.PlanBuilder(dev)
@@ -264,10 +264,10 @@ class Darknet(parts.InferMixin, nn.Module):
         ws = build.share_workspace(plist, private=slot != 0)      # (the per-device scratch is shared by everything that runs on ONE stream)
         arr = (_hip.ConvParams * len(plist))(*plist)
         # multiply-adds the MFMA pipe really executes: a Winograd layer runs 16 GEMMs over ceil(H/2)*ceil(W/2) tiles per image
-        executed = sum(2.0 * p.Cin * p.Cout * (16 * p.B * ((p.H + 1) // 2) * ((p.W + 1) // 2) if p.algo in (1, 2, 3, 4, 5) else p.ksize ** 2 * p.B * p.H * p.W)
+        executed = sum(2.0 * p.Cin * p.Cout * (16 * p.B * ((p.H + 1) // 2) * ((p.W + 1) // 2) if p.algo in _hip.ALGOS_WINO_2X2 else p.ksize ** 2 * p.B * p.H * p.W)
                        for p in plist)
         plan = dict(key=key, arr=arr, n=len(plist), first=first, head_index=head_index, head_shape=head_shape, flops=build.flops, flops_executed=executed,
-                    algos=[int(p.algo != 0) for p in plist], blks=blks, prep=prep,
+                    algos=[int(p.algo != _hip.ALGO_DIRECT) for p in plist], blks=blks, prep=prep,
                     flops0=2.0 * cin0 * blk0.conv.weight.shape[0] * 9 * B * H * W, keep=(build.keep, ws))
         self._plans.put(key, plan, build.nbytes)
         return plan
