@@ -125,7 +125,8 @@ typedef struct y2_conv_params {
     int32_t ldp, poff;   /* y_pool pixel stride and channel offset */
     int32_t out_mode;    /* 0: y[b,y,x,coff+n];  1: reorg(stride 2): y[b,y/2,x/2, coff + ((y&1)*2+(x&1))*Cout + n] */
     float slope;         /* LeakyReLU negative slope; 1.0f = no activation */
-    int32_t tile;        /* 0 = auto; else force a tile config (see conv_fwd.hip; benchmarking only).  With the fused Winograd algorithms:
+    int32_t tile;        /* 0 = auto; else force a tile config (see conv_fwd.hip; benchmarking only); an id that names no kernel of
+                          * the problem's path is refused with Y2_ENOSUP.  With the fused Winograd algorithms:
                           * 3 = the third-generation kernel (32-tile x 64-channel units, two workgroups per CU) */
     float* workspace;    /* optional scratch (16-B aligned) for the split-K remainder scheme, or NULL */
     int64_t workspace_bytes; /* its size; y2_conv_fwd_workspace_bytes() tells how much a problem can use */

@@ -31,7 +31,8 @@ GEN_TILES = (1, 2, 3, 5, 6)
 # tile id -> (BM, BN, BK) of dispatch_tile (the register-staged kernel)
 REG_TILES = {1: (128, 128, 32), 2: (128, 64, 32), 3: (64, 64, 32), 4: (256, 64, 32), 5: (64, 128, 32), 11: (128, 128, 16), 13: (64, 64, 16),
              21: (128, 128, 64), 23: (64, 64, 64)}
-ABLATIONS = (91, 92, 93)        # timing ablations of dispatch_tile: wrong results by design, nothing here may use them
+ABLATIONS = (91, 92, 93)        # ids of the removed timing ablations of dispatch_tile (wrong results by design): the library must refuse them, and 191 - 193 with them
+REFUSED_TILE_SHAPE = (1, 4, 4, 4, 4, 3)        # B, Cin, Cout, H, W, k: the smallest problem whose unknown tile id reaches dispatch_tile<false, true>'s default
 
 # x as the kernels see it: (pad, off) = extra floats per pixel row and where in the row the Cin channels start.  Multiples of 4 keep the LDS-DMA
 # and Winograd paths; the NONVEC layouts break ldx % 4 or the 16-byte alignment of x and so force conv_fwd_kernel<VEC = false>.
@@ -178,7 +179,7 @@ def route(p, pad=0, off=0, w_aligned=True, query=False):
         return _refuse(ENOSUP)
     if tile > 100:
         tile -= 100
-    if tile not in REG_TILES:
+    if tile not in REG_TILES:                                   # dispatch_tile's default: ABLATIONS are unknown ids like any other
         return _refuse(ENOSUP)
     bm, bn, bk = REG_TILES[tile]
     return made('conv_fwd_kernel', bm, bn, pool, False, taps * cdiv(p.cin, bk), NUM_CU)

@@ -53,7 +53,9 @@ def test_mirror_constants_are_the_sources():
     assert dma == fc.DMA_TILES
     reg = {int(i): (int(bm), int(bn), int(bk)) for i, bm, bn, bk in re.findall(r'case (\d+): return launch<(\d+), (\d+), \d, (\d+), POOLORD, VEC>', fwd)}
     assert reg == fc.REG_TILES
-    assert {int(i) for i in re.findall(r'case (9\d): if \(!POOLORD && VEC\)', fwd)} == set(fc.ABLATIONS)
+    dispatch_tile = re.search(r'\nint dispatch_tile\(.*?\n\}\n', fwd, re.S).group(0)
+    assert len(re.findall(r'case \d+:', dispatch_tile)) == len(fc.REG_TILES) and 'default: return Y2_ENOSUP;' in dispatch_tile
+    assert not re.findall(r'case 9\d:', dispatch_tile) and not set(fc.ABLATIONS) & set(fc.REG_TILES)       # the ablation ids fall to the default
     assert int(re.search(r'constexpr int F3_TM = (\d+);', wino).group(1)) == fc.F3_TM
     assert int(re.search(r'constexpr int WF2_DEFAULT_VARIANT = (-?\d+);', wino).group(1)) == fc.WF2_DEFAULT_VARIANT
     assert 'constexpr size_t WF_DUMP_BYTES = %d; ' % fc.WF_DUMP_BYTES in wino
@@ -249,6 +251,12 @@ def test_nothing_uses_the_ablation_ids():
     ps = [c.p for _, c in DIRECT] + list(fc.FAMILY_CASES.values()) + [r.p for r in fc.REFUSALS.values()]
     assert not {p.tile for p in ps} & ({*fc.ABLATIONS} | {100 + a for a in fc.ABLATIONS})
     assert not set(fc.REG_IDS) & set(fc.ABLATIONS)
+    for t in fc.ABLATIONS:                                                       # ... and the library refuses them where they used to launch
+        for tid in (t, t + 100):
+            for outs in ('y', 'p'):
+                assert fc.route(fc.P(*fc.REFUSED_TILE_SHAPE, tile=tid, outs=outs)).rc == fc.ENOSUP
+    r = fc.route(fc.P(*fc.REFUSED_TILE_SHAPE, tile=101))
+    assert r.rc == fc.OK and r.family == 'conv_fwd_kernel' and r.vec and not r.poolord      # the shape does reach dispatch_tile<false, true>
 
 
 # ------------------------------------------------------------------------------------------------ Winograd

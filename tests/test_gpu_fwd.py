@@ -123,8 +123,8 @@ WS_STATES = ('none', 'exact', 'short', 'misaligned')
 Result = collections.namedtuple('Result', 'rc names y yp stats ws need')
 
 
-def conv(p, ops, ws='exact', scale=True, shift=True, slope=0.1, algo=0, residual=None, x=None, ldx=None, ws_bytes=None):
-    """One y2_conv_fwd call as problem p describes it; destinations that p does not name are not given."""
+def conv(p, ops, ws='exact', scale=True, shift=True, slope=0.1, algo=0, residual=None, x=None, ldx=None, ws_bytes=None, fill=SENT):
+    """One y2_conv_fwd call as problem p describes it; destinations that p does not name are not given.  fill: what y holds before the call."""
     import _hip
     L = _hip.lib()
     Ho, Wo = fc.out_hw(p)
@@ -137,7 +137,7 @@ def conv(p, ops, ws='exact', scale=True, shift=True, slope=0.1, algo=0, residual
     if 'y' in p.outs:
         rows, width = (p.B * Ho * Wo // 4, 4 * p.cout) if p.out_mode else (p.B * Ho * Wo, p.cout)
         q.ldy, q.coff = width + YPAD, YOFF
-        y = Dest(rows * q.ldy)
+        y = Dest(rows * q.ldy, fill)
         q.y = y.ptr.value
     if 'p' in p.outs:
         q.ldp, q.poff = p.cout + YPAD, YOFF
@@ -464,6 +464,21 @@ def test_refusals_return_their_code_and_leave_the_destinations_alone(name):
     assert [n for n in r.names if n not in ('wino_input_kernel', 'wino6_in_kernel') or not name.startswith('grouped')] == []
     assert all(d is None or d.untouched() for d in (r.y, r.yp)) and (r.stats is None or not bool(r.stats.any()))
     assert (r.names != [] or bool(torch.isnan(r.ws.buf[GUARD:GUARD + r.ws.n]).all())) and r.ws.guards_intact()
+
+
+@pytest.mark.parametrize('tid', [t + h for h in (0, 100) for t in fc.ABLATIONS])
+def test_removed_ablation_ids_are_refused(tid):
+    """Tile ids 91 - 93 (191 - 193) used to launch timing ablations of the register-staged kernel that compute wrong results.  They are unknown ids now:
+    Y2_ENOSUP, nothing launched, a NaN-filled y bit for bit as it was - on the operands that tile 1 (and 101, the tile they were forms of) convolves."""
+    shape = fc.P(*fc.REFUSED_TILE_SHAPE)
+    key = key_of(shape)
+    ops = operands(key, 'randn', 'dense')
+    r = conv(shape._replace(tile=tid), ops, fill=NAN)
+    torch.cuda.synchronize()
+    assert r.rc == ENOSUP == fc.route(shape._replace(tile=tid)).rc and r.names == []
+    assert torch.equal(r.y.buf.view(torch.int32), Dest(r.y.t.numel(), NAN).buf.view(torch.int32)) and r.ws.guards_intact()
+    for good in (1, 101):
+        check(shape, conv(shape._replace(tile=good), ops), key, CONV_TOL)
 
 
 @pytest.mark.parametrize('name', list(fc.FAMILY_CASES))

@@ -30,7 +30,7 @@ def wgrad_tj(ncols, cout):
 
 
 def wgrad_plan(M, ncols, cout, groups=1):
-    """wgrad_splits and the tile choice of wgrad_impl (default mode, Y2_WGRAD_FILL unset)."""
+    """wgrad_splits and the tile choice of wgrad_impl (default mode)."""
     TI = 32 if cout <= 32 else (64 if cout <= 64 else 128)
     TJ = wgrad_tj(ncols, cout)
     tiles = cdiv(cout, TI) * cdiv(ncols, TJ)

@@ -31,12 +31,7 @@
 // ordinary row-major index.
 // y2-build-flags: -mllvm -amdgpu-mfma-vgpr-form
 //   (accumulators in ordinary VGPRs: the epilogues (affine / activation / statistics / pooled stores) read every accumulator once; from AGPRs that is a v_accvgpr_read apiece, and the kernels need 4 - 40 fewer registers)
-#include <stdlib.h>
 #include "common.h"
-
-#ifndef Y2_CONV_SPREAD
-#define Y2_CONV_SPREAD 1      // 1: issue the LDS-DMA of slab s+1 between the MFMAs of slab s (see compute_slab_spread); 0: all in front (A/B builds)
-#endif
 
 namespace {
 
@@ -240,7 +235,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
     else conv_epilogue_general<MB, NB, WM, WN, POOLORD>(a, acc, m0, n0, wm, wn, l31, half);
 }
 
-template <int BM, int BN, int WAVES_M, int BK, bool POOLORD, bool VEC, int ABLATE = 0>
+template <int BM, int BN, int WAVES_M, int BK, bool POOLORD, bool VEC>
 __global__ __launch_bounds__(NT) void conv_fwd_kernel(const ConvArgs a) {
     constexpr int LDSS = BK + 4;                 // LDS row stride (floats): (BK+4)*4 B = odd multiple of 16 B -> conflict-free b128 reads
     constexpr int SLOTS = BK / 4;                // 16-B slots per row
@@ -379,7 +374,7 @@ __global__ __launch_bounds__(NT) void conv_fwd_kernel(const ConvArgs a) {
         if (more) {
             c0 += BK;
             if (c0 >= a.Cin) { c0 = 0; ++tap; }
-            if (ABLATE != 1) load_slab(tap, c0);               // global loads in flight under the MFMAs below
+            load_slab(tap, c0);               // global loads in flight under the MFMAs below
         }
         const float* sbuf = smem + buf * STAGE;
 #pragma unroll
@@ -387,10 +382,10 @@ __global__ __launch_bounds__(NT) void conv_fwd_kernel(const ConvArgs a) {
             f32x4 fa4[MB], fb4[NB];
 #pragma unroll
             for (int i = 0; i < MB; ++i)
-                fa4[i] = (ABLATE == 3) ? ra[i] : *reinterpret_cast<const f32x4*>(sbuf + fa + i * 32 * LDSS + 8 * q);
+                fa4[i] = *reinterpret_cast<const f32x4*>(sbuf + fa + i * 32 * LDSS + 8 * q);
 #pragma unroll
             for (int j = 0; j < NB; ++j)
-                fb4[j] = (ABLATE == 3) ? rb[j] : *reinterpret_cast<const f32x4*>(sbuf + fb + j * 32 * LDSS + 8 * q);
+                fb4[j] = *reinterpret_cast<const f32x4*>(sbuf + fb + j * 32 * LDSS + 8 * q);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -399,10 +394,8 @@ __global__ __launch_bounds__(NT) void conv_fwd_kernel(const ConvArgs a) {
                     for (int j = 0; j < NB; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa4[i][e], fb4[j][e], acc[i][j], 0, 0, 0);
         }
-        if (ABLATE != 2) {
-            if (more) store_slab(buf ^ 1);
-            __syncthreads();
-        }
+        if (more) store_slab(buf ^ 1);
+        __syncthreads();
     }
 
     conv_epilogue<MB, NB, WM, WN, POOLORD>(a, acc, m0, n0, wm, wn, l31, half);
@@ -426,10 +419,10 @@ __global__ __launch_bounds__(NT) void conv_fwd_kernel(const ConvArgs a) {
 // the current tile's last slab, so its DMA latency runs under the last slab's MFMAs and the epilogue.  Aimed at the short-K layers (1x1
 // convolutions: 2 ... 32 slabs per tile), where every tile of the one-tile-per-workgroup form starts with an exposed first fetch - and
 // all workgroups of a CU reach that point together, because they were launched together and their tiles cost the same.
-template <int BM, int BN, int WAVES_M, bool POOLORD, bool CTAIL, int STAGES = 2, bool GEN = false, int NTH = NT, bool PERSIST = false>
+template <int BM, int BN, int WAVES_M, bool POOLORD, bool CTAIL, bool GEN = false, int NTH = NT, bool PERSIST = false>
 __global__ __launch_bounds__(NTH) void conv_fwd_dma_kernel(const ConvArgs a) {
     constexpr int BK = 32;
-    static_assert(!PERSIST || (!GEN && STAGES == 2), "the persistent form covers the standard two-stage kernel");
+    static_assert(!PERSIST || !GEN, "the persistent form covers the standard kernel");
     constexpr int WAVES_N = (NTH / 64) / WAVES_M;
     constexpr int RPP = NTH / 8;                  // rows staged per DMA pass (8 lanes per 128-B row)
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
@@ -616,7 +609,7 @@ __global__ __launch_bounds__(NTH) void conv_fwd_dma_kernel(const ConvArgs a) {
     };
 
     // one DMA instruction of a standard slab (piece j < AR: A rows, else B rows): the pieces of slab s+1 can be issued one by one
-    // BETWEEN the MFMAs of slab s (Y2_CONV_SPREAD) instead of all in front of them
+    // BETWEEN the MFMAs of slab s (compute_slab_spread) instead of all in front of them
     auto issue_piece = [&](int tap, int c0, int buf, int j) {
         float* sa = smem + buf * STAGE + wave * (8 * BK);
         float* sb = sa + BM * BK;
@@ -750,47 +743,22 @@ __global__ __launch_bounds__(NTH) void conv_fwd_dma_kernel(const ConvArgs a) {
     const int nk = ks1 - ks0;
     int tap = GEN ? 0 : ks0 / a.cchunks, c0 = GEN ? 0 : (ks0 % a.cchunks) * BK;
     if (nk > 0) {
-        if (STAGES == 2) {
-            issue_slab(ks0, tap, c0, 0);
-            for (int ks = 0; ks < nk - 1; ++ks) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of slab ks has landed
-                __syncthreads();                                     // ... everybody's has, and nobody still reads the other buffer
-                c0 += BK;
-                if (c0 >= a.Cin) { c0 = 0; ++tap; }
-                if (Y2_CONV_SPREAD && !GEN) {
-                    compute_slab_spread(ks & 1, tap, c0, (ks + 1) & 1);
-                } else {
-                    issue_slab(ks0 + ks + 1, tap, c0, (ks + 1) & 1);
-                    compute_slab(ks & 1);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            compute_slab((nk - 1) & 1);
-        } else {
-            // 3-deep ring: the DMA of slab s+2 is issued before slab s is consumed, so one slab stays in flight ACROSS the
-            // barrier (counted vmcnt + raw s_barrier: __syncthreads() would drain the DMA queue, cdna guide "glds span").
-            issue_slab(ks0, tap, c0, 0);
-            if (nk > 1) {
-                c0 += BK;
-                if (c0 >= a.Cin) { c0 = 0; ++tap; }
-                issue_slab(ks0 + 1, tap, c0, 1);
-            }
-            int cur = 0, nxt = 2;
-            for (int ks = 0; ks < nk; ++ks) {
-                if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AR + BR) : "memory");   // slab ks landed, ks+1 may be in flight
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();        // everyone's part of slab ks is in LDS; everyone finished reading slab ks-1
-                if (ks + 2 < nk) {
-                    c0 += BK;
-                    if (c0 >= a.Cin) { c0 = 0; ++tap; }
-                    issue_slab(ks0 + ks + 2, tap, c0, nxt);         // overwrites the buffer of slab ks-1
-                }
-                compute_slab(cur);
-                cur = cur == 2 ? 0 : cur + 1;
-                nxt = nxt == 2 ? 0 : nxt + 1;
+        issue_slab(ks0, tap, c0, 0);
+        for (int ks = 0; ks < nk - 1; ++ks) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of slab ks has landed
+            __syncthreads();                                     // ... everybody's has, and nobody still reads the other buffer
+            c0 += BK;
+            if (c0 >= a.Cin) { c0 = 0; ++tap; }
+            if (!GEN) {
+                compute_slab_spread(ks & 1, tap, c0, (ks + 1) & 1);
+            } else {
+                issue_slab(ks0 + ks + 1, tap, c0, (ks + 1) & 1);
+                compute_slab(ks & 1);
             }
         }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        compute_slab((nk - 1) & 1);
     }
 
     if (is_split) {
@@ -862,16 +830,15 @@ __global__ __launch_bounds__(NTHR) void conv_splitk_fixup_kernel(const ConvArgs 
     conv_epilogue<MB, NB, WM, WN, POOLORD>(a, acc, tile_m * BM, tile_n * BN, wm, wn, l31, half);
 }
 
-template <int BM, int BN, int WAVES_M, int BK, bool POOLORD, bool VEC, int ABLATE = 0>
+template <int BM, int BN, int WAVES_M, int BK, bool POOLORD, bool VEC>
 int launch(const ConvArgs& a0, hipStream_t stream) {
     ConvArgs a = a0;
     a.tiles_m = y2_cdiv(a.M, BM);
     a.epi_bm = BM; a.epi_bn = BN;
     a.tiles_n = y2_cdiv(a.Cout, BN);
-    size_t lds = 2u * (BM + BN) * (BK + 4) * sizeof(float);
-    if (const char* pad = getenv("Y2_CONV_LDS_MIN")) { const size_t m = (size_t)atol(pad); if (lds < m) lds = m; }   // occupancy experiments only
+    const size_t lds = 2u * (BM + BN) * (BK + 4) * sizeof(float);
     a.cchunks = y2_cdiv(a.Cin, BK);
-    auto kern = conv_fwd_kernel<BM, BN, WAVES_M, BK, POOLORD, VEC, ABLATE>;
+    auto kern = conv_fwd_kernel<BM, BN, WAVES_M, BK, POOLORD, VEC>;
     static Y2LdsAttr attr_set;
     if (const int rc = attr_set.ensure(reinterpret_cast<const void*>(kern))) return rc;
     const long long grid = (long long)a.tiles_m * a.tiles_n;
@@ -910,8 +877,7 @@ int launch_dma(const ConvArgs& a0, hipStream_t stream, float* ws, size_t ws_byte
     a.epi_bm = BM; a.epi_bn = BN;
     a.tiles_n = y2_cdiv(a.Cout, BN);
     a.cchunks = y2_cdiv(a.Cin, 32);
-    size_t lds = 2u * (BM + BN) * 32 * sizeof(float);
-    if (const char* pad = getenv("Y2_CONV_LDS_MIN")) { const size_t m = (size_t)atol(pad); if (lds < m) lds = m; }   // occupancy experiments only
+    const size_t lds = 2u * (BM + BN) * 32 * sizeof(float);
     const bool ctail = !GEN && (a.Cin % 32) != 0;
     const int nk_all = GEN ? y2_cdiv(a.K, 32) : a.taps * a.cchunks;
     const long long tiles = (long long)a.tiles_m * a.tiles_n * (a.groups > 1 ? a.groups : 1);
@@ -927,7 +893,7 @@ int launch_dma(const ConvArgs& a0, hipStream_t stream, float* ws, size_t ws_byte
         if (GEN || ctail || a.groups > 1) return Y2_ENOSUP;
         if (ws_need != nullptr) { *ws_need = 0; return Y2_OK; }
         a.full_tiles = (int)tiles; a.ksplit = 1; a.partial = nullptr;
-        auto kern = conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, false, 2, false, NTH, PERSIST>;
+        auto kern = conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, false, false, NTH, PERSIST>;
         static Y2LdsAttr attr_p;
         if (const int rc_ = attr_p.ensure(reinterpret_cast<const void*>(kern))) return rc_;
         static int resident = 0;                           // workgroups one CU holds (registers, LDS), asked once per instantiation
@@ -947,19 +913,16 @@ int launch_dma(const ConvArgs& a0, hipStream_t stream, float* ws, size_t ws_byte
     plan_split(tiles, nk_all, (long long)BM * BN, ws != nullptr ? ws_bytes : 0, a.full_tiles, a.ksplit);
     a.partial = ws;
     const long long grid = a.full_tiles + (tiles - a.full_tiles) * a.ksplit;
-    static Y2LdsAttr attr_set[4];
-    static int stages3 = -1;
-    if (stages3 < 0) { const char* e = getenv("Y2_CONV_STAGES"); stages3 = (e != nullptr && atoi(e) == 3) ? 1 : 0; }
-#define Y2_DMA_LAUNCH(KERN, SLOT, LDSB)                                                                                     \
+    static Y2LdsAttr attr_set[3];
+#define Y2_DMA_LAUNCH(KERN, SLOT)                                                                                           \
     do {                                                                                                                    \
         auto kern = KERN;                                                                                                   \
         if (const int rc_ = attr_set[SLOT].ensure(reinterpret_cast<const void*>(kern))) return rc_;                        \
-        Y2_LAUNCH(a.groups > 1 ? "conv_fwd_dma_kernel[grouped]" : "conv_fwd_dma_kernel", 2.0 * (double)a.M * a.Cout * (a.K > 0 ? a.K : a.taps * a.Cin) * (a.groups > 1 ? a.groups : 1), kern, dim3((unsigned)grid), dim3(NTH), LDSB, stream, a);                                         \
+        Y2_LAUNCH(a.groups > 1 ? "conv_fwd_dma_kernel[grouped]" : "conv_fwd_dma_kernel", 2.0 * (double)a.M * a.Cout * (a.K > 0 ? a.K : a.taps * a.Cin) * (a.groups > 1 ? a.groups : 1), kern, dim3((unsigned)grid), dim3(NTH), lds, stream, a);                                         \
     } while (0)
-    if (GEN) Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, false, false, 2, true, NTH>), 3, lds);
-    else if (stages3 && !ctail) Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, false, 3, false, NTH>), 2, lds / 2 * 3);
-    else if (ctail) Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, true, 2, false, NTH>), 1, lds);
-    else Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, false, 2, false, NTH>), 0, lds);
+    if (GEN) Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, false, false, true, NTH>), 2);
+    else if (ctail) Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, true, false, NTH>), 1);
+    else Y2_DMA_LAUNCH((conv_fwd_dma_kernel<BM, BN, WAVES_M, POOLORD, false, false, NTH>), 0);
 #undef Y2_DMA_LAUNCH
     if (a.ksplit > 1)
         Y2_LAUNCH("conv_splitk_fixup_kernel", 0.0, (conv_splitk_fixup_kernel<BM, BN, WAVES_M, (POOLORD && !GEN), NTH>), dim3((unsigned)(tiles - a.full_tiles)), dim3(NTH), 0, stream, a);
@@ -976,9 +939,10 @@ int launch_dma(const ConvArgs& a0, hipStream_t stream, float* ws, size_t ws_byte
 //   * LDS-DMA with the XOR swizzle of the 64-B-row geometry: physical 16-B slot p of row r holds logical chunk p ^ ((r>>2)&3)
 //     (4 rows share one 256-B bank row), fragment reads apply the same involution -> conflict-free ds_read_b128;
 //   * per slab: 8 DMA instructions, 8 ds_read_b128, 32 MFMAs (2048 cycles) and no s_barrier at all.
-template <bool POOLORD, int STAGES = 4, int BK = 16>
+template <bool POOLORD>
 __global__ __launch_bounds__(64) void conv_fwd_wave_kernel(const ConvArgs a) {
     constexpr int TM = 64, TN = 64;
+    constexpr int STAGES = 4, BK = 16;               // ring depth, floats of K per slab (launch_wave sizes the LDS by the same two)
     constexpr int CH = BK / 4;                       // 16-B chunks per row
     constexpr int RP = 64 / CH;                      // rows per DMA instruction
     constexpr int NP = 64 / RP;                      // DMA instructions per operand per slab
@@ -1004,9 +968,9 @@ __global__ __launch_bounds__(64) void conv_fwd_wave_kernel(const ConvArgs a) {
     const int m0 = tile_m * TM, n0 = tile_n * TN;
 
     // staging: lane -> physical slot p = lane % CH of row lane / CH + RP*i; it fetches logical chunk p ^ swz(row)
-    // swz: rows sharing one 256-B bank row get different XOR masks (BK = 16: 4 rows per bank row; BK = 32: 2 rows)
+    // swz: the 4 rows sharing one 256-B bank row get different XOR masks
     const int srow = lane / CH;
-    const int lchunk = (lane % CH) ^ (BK == 32 ? ((srow >> 1) & 7) : ((srow >> 2) & 3));
+    const int lchunk = (lane % CH) ^ ((srow >> 2) & 3);
     unsigned a_base[NP], a_mask[NP], b_base[NP];
     const int up_left = (a.taps == 9) ? (a.W + 1) : 0;
     const int ktot = a.taps * a.Cin;
@@ -1062,7 +1026,7 @@ __global__ __launch_bounds__(64) void conv_fwd_wave_kernel(const ConvArgs a) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     // fragment offsets (floats): row l31 (+32 per block), logical chunk 2q + half -> physical chunk (same involution)
-    const int sw = BK == 32 ? ((l31 >> 1) & 7) : ((l31 >> 2) & 3);
+    const int sw = (l31 >> 2) & 3;
     int foff[QG];
 #pragma unroll
     for (int q = 0; q < QG; ++q) foff[q] = l31 * BK + (((2 * q + half) ^ sw) << 2);
@@ -1088,8 +1052,7 @@ __global__ __launch_bounds__(64) void conv_fwd_wave_kernel(const ConvArgs a) {
     constexpr int PER = 2 * NP;                       // DMA instructions per slab
     auto wait_slab = [&](int ks, int nk) {             // slab ks landed; up to min(STAGES-2, nk-1-ks) younger slabs stay in flight
         const int ahead = min(STAGES - 2, nk - 1 - ks);
-        if (ahead >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER) : "memory");
-        else if (ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
+        if (ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
         else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
@@ -1168,8 +1131,7 @@ int launch_wave(const ConvArgs& a0, hipStream_t stream, float* ws, size_t ws_byt
     ConvArgs a = a0;
     a.tiles_m = y2_cdiv(a.M, 64);
     a.tiles_n = y2_cdiv(a.Cout, 64);
-    const char* bke = getenv("Y2_WAVE_BK");
-    const int nk_all = a.taps * (a.Cin / ((bke && atoi(bke) == 32) ? 32 : 16));
+    const int nk_all = a.taps * (a.Cin / 16);
     const long long tiles = (long long)a.tiles_m * a.tiles_n;
     if (tiles <= 0 || tiles > 0x7fffffffLL) return Y2_EINVAL;
     const int P = 4 * Y2_NUM_CU;     // one tile stream per SIMD
@@ -1182,21 +1144,8 @@ int launch_wave(const ConvArgs& a0, hipStream_t stream, float* ws, size_t ws_byt
     plan_split(tiles, nk_all, 64 * 64, ws != nullptr ? ws_bytes : 0, a.full_tiles, a.ksplit, P);
     a.partial = ws;
     const long long grid = a.full_tiles + (tiles - a.full_tiles) * a.ksplit;
-    static int stages = -1, bk = 16;
-    if (stages < 0) { const char* e = getenv("Y2_WAVE_STAGES"); stages = e ? atoi(e) : 4; const char* b = getenv("Y2_WAVE_BK"); bk = (b && atoi(b) == 32) ? 32 : 16; }
-    if (bk == 32 && (a.Cin % 32) != 0) return Y2_ENOSUP;
-    const size_t lds = (size_t)stages * (64 + 64) * bk * sizeof(float);
-    static bool attr = false;
-#define Y2_WAVE(ST, BKV)                                                                                                          \
-    do {                                                                                                                          \
-        auto kern = conv_fwd_wave_kernel<POOLORD, ST, BKV>;                                                                       \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        Y2_LAUNCH("conv_fwd_wave_kernel", 2.0 * (double)a.M * a.Cout * (a.K > 0 ? a.K : a.taps * a.Cin) * (a.groups > 1 ? a.groups : 1), kern, dim3((unsigned)grid), dim3(64), lds, stream, a);                                                 \
-    } while (0)
-    (void)attr;
-    if (bk == 32) { if (stages == 2) Y2_WAVE(2, 32); else if (stages == 3) Y2_WAVE(3, 32); else Y2_WAVE(4, 32); }
-    else { if (stages == 2) Y2_WAVE(2, 16); else if (stages == 3) Y2_WAVE(3, 16); else Y2_WAVE(4, 16); }
-#undef Y2_WAVE
+    const size_t lds = (size_t)4 * (64 + 64) * 16 * sizeof(float);      // the kernel's STAGES x (TM + TN) x BK
+    Y2_LAUNCH("conv_fwd_wave_kernel", 2.0 * (double)a.M * a.Cout * (a.K > 0 ? a.K : a.taps * a.Cin) * (a.groups > 1 ? a.groups : 1), conv_fwd_wave_kernel<POOLORD>, dim3((unsigned)grid), dim3(64), lds, stream, a);
     if (a.ksplit > 1)
         Y2_LAUNCH("conv_splitk_fixup_kernel", 0.0, (conv_splitk_fixup_kernel<64, 64, 1, POOLORD, 64>), dim3((unsigned)(tiles - a.full_tiles)), dim3(64), 0, stream, a);
     Y2_LAUNCH_CHECK();
@@ -1232,9 +1181,6 @@ int dispatch_tile(const ConvArgs& a, int tile, hipStream_t s) {
         case 4: return launch<256, 64, 4, 32, POOLORD, VEC>(a, s);
         case 5: return launch<64, 128, 2, 32, POOLORD, VEC>(a, s);
         case 11: return launch<128, 128, 2, 16, POOLORD, VEC>(a, s);
-        case 91: if (!POOLORD && VEC) return launch<128, 128, 2, 32, false, true, 1>(a, s); return Y2_ENOSUP;   // timing ablations (wrong results)
-        case 92: if (!POOLORD && VEC) return launch<128, 128, 2, 32, false, true, 2>(a, s); return Y2_ENOSUP;
-        case 93: if (!POOLORD && VEC) return launch<128, 128, 2, 32, false, true, 3>(a, s); return Y2_ENOSUP;
         case 13: return launch<64, 64, 2, 16, POOLORD, VEC>(a, s);
         case 21: return launch<128, 128, 2, 64, POOLORD, VEC>(a, s);
         case 23: return launch<64, 64, 2, 64, POOLORD, VEC>(a, s);

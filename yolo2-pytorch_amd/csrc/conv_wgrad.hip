@@ -17,12 +17,7 @@
 // wave against 16 KB + 16 KB of DMA: the same MFMA-bound balance as the forward kernel.
 // y2-build-flags: -mllvm -amdgpu-mfma-vgpr-form
 //   (accumulators in ordinary VGPRs: same reason as conv_fwd.hip: no v_accvgpr_read in front of the partial-sum stores, up to 43 fewer registers)
-#include <stdlib.h>
 #include "common.h"
-
-#ifndef Y2_WGRAD_SPREAD
-#define Y2_WGRAD_SPREAD 1     // 1: LDS-DMA of slab s+1 between the MFMAs of slab s; 0: all in front (A/B builds)
-#endif
 
 namespace {
 
@@ -377,15 +372,10 @@ __global__ __launch_bounds__(NT) void conv_wgrad_kernel(const WgradArgs a) {
         compute_slab_checked((nk - 1) & 1);
     } else {
         for (int ks = 0; ks < nk - 1; ++ks) {
-            if (Y2_WGRAD_SPREAD) plan_slab(slab_lo + ks + 1);      // VALU only: overlaps the tail of the previous slab's MFMAs
+            plan_slab(slab_lo + ks + 1);      // VALU only: overlaps the tail of the previous slab's MFMAs
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (Y2_WGRAD_SPREAD) {
-                compute_slab_spread(ks & 1, (ks + 1) & 1);
-            } else {
-                issue_slab(slab_lo + ks + 1, (ks + 1) & 1);
-                compute_slab(ks & 1);
-            }
+            compute_slab_spread(ks & 1, (ks + 1) & 1);      // LDS-DMA of slab ks+1 between the MFMAs of slab ks
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -440,8 +430,7 @@ static int wgrad_splits(long long M, int ncols, int Cout, int groups, int* slabs
     // ones): one full wave of workgroups.  More splits only add atomic epilogues (measured, B=64: the 1x1 layers 0.130 -> 0.120 ms and
     // the 52x52 / 26x26 grouped reductions 0.43 -> 0.41 with 2 instead of 4 for the 128x128 tile; the 64x64-tile 208x208 layer
     // 1.02 -> 1.50 the other way)
-    static const int fill_env = getenv("Y2_WGRAD_FILL") != nullptr ? atoi(getenv("Y2_WGRAD_FILL")) : 0;
-    const int fill = fill_env > 0 ? fill_env : (TI * TJ >= 128 * 128 ? 2 : (TI * TJ >= 128 * 64 ? 3 : 4));
+    const int fill = TI * TJ >= 128 * 128 ? 2 : (TI * TJ >= 128 * 64 ? 3 : 4);
     int splits = y2_cdiv(fill * Y2_NUM_CU, tiles * groups);
     const int max_splits = slabs / 8 > 0 ? slabs / 8 : 1;
     if (splits > max_splits) splits = max_splits;

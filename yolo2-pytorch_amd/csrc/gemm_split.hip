@@ -165,7 +165,7 @@ struct GemmSplitArgs {
     long long gA, gB, gC;      // elements per group
     int M, N, K, ldc, tiles_m, tiles_n, groups;
     float out_scale;           // C = (acc) * out_scale (the fp16 variant's operands carry power-of-two scales)
-    long long* stamps;         // debug builds (-DY2_STAMPS): cycle stamps of workgroup 0
+    long long unused_ = 0;     // holds a_bytes / b_bytes at the kernarg offsets the kernels' scalar loads were scheduled around (without it the compiler emits 4 - 13 more instructions per kernel)
     unsigned a_bytes, b_bytes; // bytes from a group's plane-0 slice to the end of its plane-2 slice (the buffer range; masked rows use an offset beyond it)
 };
 
@@ -328,29 +328,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_split_kernel(const GemmSplitArgs
         for (int j = NMFMA / EVERY; prefetch && j < NDMA; ++j) issue_piece(k_next, slot_next, j);
     };
 
-#ifdef Y2_STAMPS
-    // per-stage cycle stamps of wave 0 of workgroup 0 (s_memtime): [stage][0] before the DMA wait, [1] after it, [2] after the barrier, [3] after the MFMAs
-    long long* stamps = (blockIdx.x == 0 && t == 0) ? a.stamps : nullptr;
-#define Y2_STAMP(ks_, w_) do { if (stamps != nullptr && (ks_) < 64) stamps[(ks_) * 4 + (w_)] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define Y2_STAMP(ks_, w_) do { } while (0)
-#endif
-#ifdef Y2_STAMPS
-    if (stamps != nullptr) { stamps[252] = (long long)__builtin_readcyclecounter(); stamps[253] = (long long)__builtin_amdgcn_s_memrealtime(); }
-#endif
     issue_slab(0, 0);
     if (nk > 1) issue_slab(BK, 1);
     int cur = 0, nxt = 2;
     // (the prefetching and the draining iterations are separate loops: one loop body with a branch would make the accumulators meet in
     // phi nodes and cost an accumulator copy per MFMA, see conv_wgrad.hip)
     for (int ks = 0; ks + 2 < nk; ++ks) {
-        Y2_STAMP(ks, 0);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");      // slab ks landed; slab ks+1 may still be in flight
-        Y2_STAMP(ks, 1);
         __builtin_amdgcn_s_barrier();        // everyone's part of slab ks is in LDS; everyone finished reading slab ks-1 (whose slot is refilled now)
-        Y2_STAMP(ks, 2);
         compute_slab(std::true_type{}, cur, (ks + 2) * BK, nxt);
-        Y2_STAMP(ks, 3);
         cur = cur == 2 ? 0 : cur + 1;
         nxt = nxt == 2 ? 0 : nxt + 1;
     }
@@ -364,9 +350,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_split_kernel(const GemmSplitArgs
     __builtin_amdgcn_s_barrier();
     compute_slab(std::false_type{}, cur, 0, 0);
 
-#ifdef Y2_STAMPS
-    if (stamps != nullptr) { stamps[254] = (long long)__builtin_readcyclecounter(); stamps[255] = (long long)__builtin_amdgcn_s_memrealtime(); }
-#endif
     // ---- store: register r of block (i, j) is row 8*(r>>2) + 4*half + (r&3), column l31: a wave writes 128-B row segments
     float* C = a.C + (size_t)grp * a.gC;
 #pragma unroll
@@ -419,10 +402,6 @@ int y2_internal_gemm_split(const void* A, long long planeA, const void* B, long 
     const long long grid = (long long)a.tiles_m * a.tiles_n * groups;
     if (grid > 0x7fffffffLL || M > 0x7fffffffLL) return Y2_EINVAL;
     a.out_scale = out_scale;
-    a.stamps = nullptr;
-#ifdef Y2_STAMPS
-    if (const char* sp = getenv("Y2_GS_STAMPS_PTR")) a.stamps = reinterpret_cast<long long*>(strtoull(sp, nullptr, 0));
-#endif
     const char* e = getenv("Y2_SPLIT_BK");            // 16: 24 KB stages, two workgroups per CU; 32 (default): 48 KB stages, one (A/B runs)
     const int bk = (e != nullptr && atoi(e) == 16) ? 16 : 32;
     const char* e2 = getenv("Y2_SPLIT_WAVES");        // 4: one wave per SIMD (wave tile 64 x 64); 8 (default): two (64 x 32)

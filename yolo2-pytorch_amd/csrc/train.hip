@@ -1187,8 +1187,7 @@ extern "C" int y2_maxpool_bwd(const float* x, const float* dy, const float* dy2,
     if (Ho <= 0 || Wo <= 0) return Y2_EINVAL;
     const long long total = (long long)B * H * W * C;
     const bool aligned = !(C & 3) && !(ldx & 3) && !(ldy & 3) && !(lddx & 3) && y2_aligned16(x) && y2_aligned16(dy) && y2_aligned16(dx) && (!dy2 || y2_aligned16(dy2));
-    static const bool tiled_env = getenv("Y2_POOL_BWD_TILED") == nullptr || atoi(getenv("Y2_POOL_BWD_TILED")) != 0;
-    if (tiled_env && aligned && ksize == 3 && stride == 2 && pad == 1 && !(C % MP_CH) && (long long)B * (C / MP_CH) < 65535 && (long long)H * W * ldx < 0x7fffffffLL) {
+    if (aligned && ksize == 3 && stride == 2 && pad == 1 && !(C % MP_CH) && (long long)B * (C / MP_CH) < 65535 && (long long)H * W * ldx < 0x7fffffffLL) {
         const dim3 grid((unsigned)y2_cdiv(W, MP_TW), (unsigned)y2_cdiv(H, MP_TH), (unsigned)(B * (C / MP_CH)));
         Y2_LAUNCH("maxpool_bwd_kernel", 0.0, maxpool3s2_bwd_kernel, grid, dim3(256), 0, y2_s(stream), x, dy, dy2, dx, H, W, Ho, Wo, C / MP_CH, ldx, ldy, lddx);
         Y2_LAUNCH_CHECK();

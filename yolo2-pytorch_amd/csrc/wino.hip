@@ -260,11 +260,7 @@ __device__ __forceinline__ f32x4 y2_pk_sub(f32x4 a, f32x4 b) {
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
 
-#ifdef Y2_STAMPS
-constexpr size_t WF_DUMP_BYTES = 1024 + 8192;
-#else
 constexpr size_t WF_DUMP_BYTES = 1024;      // where the lanes of pixels / tiles / channels that do not exist store (branch-free epilogue)
-#endif
 constexpr int WF_POS_FLOATS = (64 + 64) * 32;      // one position's A + B slab (16 KB)
 constexpr int WF2_DEFAULT_VARIANT = 3;             // which fused kernel y2_conv_fwd launches by default: -1 = first generation, else the feature mask of wino_fused2_kernel
 
@@ -534,7 +530,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // ~100 registers; dword "touch" loads one stage ahead as a cache prefetch: +1-7 %; pixels by LDS-DMA into a scratch area and read
 // back: -1-3 % (not worth 32 KB of LDS); every row loaded as early as its register frees: +4-24 % (tile-transition spills).
 // What DID help were registers: pixel offsets formed at the load instead of 32 hoisted sums, the decode-table loads from one
-// base address, the DMA plane offsets as s_mul - each 3-8 %.  Per-stage stamps (-DY2_STAMPS): a stage costs 4.45k cycles with
+// base address, the DMA plane offsets as s_mul - each 3-8 %.  Per-stage cycle stamps (a debug build since removed, docs/history): a stage costs 4.45k cycles with
 // DMA'd V, 4.55k with the transform's adds and stores but no pixel loads, 5.0k with 8 pixel loads.
 // VAR bit 3: Cin == 32, one K slab per tile (the 208x208 layer).
 template <int VAR, int OUT>     // OUT: bit 0 = full-resolution output y, bit 1 = pooled output, bit 2 = BatchNorm statistics
@@ -736,17 +732,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int pp = 0; pp < PG; ++pp) *reinterpret_cast<f32x4*>(smem + t * 4 + pp * WF_POS_FLOATS + i * 32 * 32) = col_combine(sv, pp);
         }
     }
-    // -DY2_STAMPS (tools/wf_bench.py --stamps): wave 0 of workgroup 0 records s_memtime behind every stage barrier and around the
-    // epilogue (in LDS - a global store would sit in the vmcnt queue of the loads being timed - copied out behind the dump area at
-    // the end; the host side reserves the room in the same build).  Caveat: the extra state changes the register allocation of the
-    // tile transition; the steady-state stages are what these stamps are good for.
-#ifdef Y2_STAMPS
-    unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(smem + 2 * STAGE_FLOATS);
-    int nstamp = 0;
-#define Y2_STAMP() do { if (blockIdx.x == 0 && wave == 0 && nstamp < 1000) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[nstamp] = tm_; ++nstamp; } } while (0)
-#else
-#define Y2_STAMP() do {} while (0)
-#endif
     for (;;) {
         const int em0 = fm0, en0 = fn0;           // this tile's origin (the fetch cursor is still on this tile)
         if (!Z1::value) {
@@ -758,8 +743,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #define Y2_WF2_SYNC()                                              \
         if (RAWIN) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   /* + this wave's ds_write of V */ \
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      \
-        __builtin_amdgcn_s_barrier();                              \
-        Y2_STAMP()
+        __builtin_amdgcn_s_barrier()
         // first K slab (never the last one unless ONE): the four accumulator groups start from the MFMA's zero operand
         using ZL = std::integral_constant<bool, ONE>;
         if (!ONE) {
@@ -818,7 +802,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             stage(S1{}, &acc[12], F_{}, 0, G0{}, ZL{});
         }
 #undef Y2_WF2_SYNC
-        Y2_STAMP();
         // ---- epilogue: output transform A^T M A in registers (accumulator register r of the 16 positions belongs to the same
         //      (tile row, channel)), then affine + LeakyReLU, pooling, statistics, stores - branch-free
         float s1 = 0.f, s2 = 0.f;
@@ -865,14 +848,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 atomicAdd(st + a.Cout + pn, (double)s2);
             }
         }
-        Y2_STAMP();
         if (!more) break;
     }
-#ifdef Y2_STAMPS
-    if (blockIdx.x == 0 && wave == 0)
-        for (int i = lane; i < 1000; i += 64) reinterpret_cast<unsigned long long*>(a.dump + 256)[i] = i < nstamp ? stamps[i] : 0ull;
-#endif
-#undef Y2_STAMP
 }
 
 // ---- fused kernel, third generation: TWO workgroups per CU.  wino_fused2_kernel runs one wave per SIMD (256 accumulator
@@ -1983,10 +1960,9 @@ extern "C" int y2_wino_wgrad_ex(const float* x, const float* dz, float* dw_packe
     const float* Vsrc = v_transformed != nullptr ? v_transformed : V;
 
     // the gradient operand dM = A dz A^T: formed in the loader of the grouped reduction from the raw gradient (no wino_dz_kernel, no 4x tensor) -
-    // Y2_WGRAD_DZRAW=0: the three-step form (A/B runs, and the fallback when the raw gradient does not fit one buffer descriptor)
-    static const bool dzraw_env = getenv("Y2_WGRAD_DZRAW") == nullptr || atoi(getenv("Y2_WGRAD_DZRAW")) != 0;
+    // for Cout <= 256; otherwise the three-step form (also the fallback when the raw gradient does not fit one buffer descriptor)
     int rc = Y2_ENOSUP;
-    if (dzraw_env && !y2_det.on && Cout <= 256) {      // measured (B=64): 104x104 64->128 0.99 -> 0.80 ms, 52x52 128->256 0.63 -> 0.56; 26x26 256->512 0.49 -> 0.52, 13x13 layers +15-20 %
+    if (!y2_det.on && Cout <= 256) {      // measured (B=64): 104x104 64->128 0.99 -> 0.80 ms, 52x52 128->256 0.63 -> 0.56; 26x26 256->512 0.49 -> 0.52, 13x13 layers +15-20 %
         int32_t* table = reinterpret_cast<int32_t*>(DM);                 // (the tensor's place in the workspace)
         Y2_LAUNCH("wino_tile_table_kernel", 0.0, wino_tile_table_kernel, dim3((unsigned)y2_cdiv(T, 256)), dim3(256), 0, s, table, (int)T, H, W, th, tw, ia.d_tt, ia.d_tw, (int32_t*)nullptr, 0);
         rc = y2_internal_wgrad_grouped_dz(Vsrc, dz, table, DU, T, Cin, Cout, ldz, W, (unsigned long long)B * H * W * ldz * 4ull, T * Cin, (long long)Cout * Cin, stream);
