@@ -224,6 +224,13 @@ long long y2_conv_fwd_workspace_bytes(const y2_conv_params* p);
  * model/yolo2.py:125-130 runs them as separate nn.Module calls). Stops at the first error. */
 int y2_conv_fwd_batch(const y2_conv_params* params, int count, y2_stream_t stream);
 
+/* y2_conv_fwd(p) for a raw 3x3 problem (scale == shift == NULL, slope == 1, y given, y_pool NULL) as a producer of z_sel (see y2_bn_act_fwd_sel): the same
+ * launch also writes z_sel [B,H/2,W/2,Cout] (pixel stride ldzs) = per 2x2 window the first z_q in scan order that maximises sign(gamma[c]) * z_q (strict
+ * comparison, gamma[c] == 0: q = 0; gamma = the BatchNorm weight).  Served only by the fused Winograd kernel of tile 3: p->algo is Y2_ALGO_WINOGRAD_FUSED or
+ * Y2_ALGO_WINOGRAD_IMPLICIT with p->tile == 3, H and W even, z_sel 16-byte aligned, ldzs >= Cout a multiple of 4, outputs below 2 GB.  Anything else:
+ * Y2_ENOSUP with nothing launched and nothing written (call y2_conv_fwd and y2_bn_act_fwd_sel instead); gamma or z_sel NULL: Y2_EINVAL.  p->stats may be NULL. */
+int y2_conv_fwd_sel(const y2_conv_params* p, const float* gamma, float* z_sel, int ldzs, y2_stream_t stream);
+
 /* First layer (model/yolo2.py:78, 'layers1.0'): reads the plugin's NCHW fp32 input [B,Cin<=4,H,W] directly,
  * conv3x3 pad 1 -> affine -> LeakyReLU -> (optional 2x2 max-pool), writes NHWC.
  * w is the UNPACKED state_dict weight [Cout][Cin][3][3]; Cout <= 64.  y (full res, pixel stride ldy) and/or

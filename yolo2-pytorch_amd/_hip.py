@@ -95,6 +95,7 @@ SIGNATURES = {
     'y2_unpack_weight_grad': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     'y2_bn_fold': [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
     'y2_conv_fwd': [ctypes.POINTER(ConvParams), c_void_p],
+    'y2_conv_fwd_sel': [ctypes.POINTER(ConvParams), c_void_p, c_void_p, c_int, c_void_p],
     'y2_conv_fwd_workspace_bytes': [ctypes.POINTER(ConvParams)],
     'y2_wino_weight': [c_void_p, c_void_p, c_int, c_int, c_void_p],
     'y2_wino6_weight': [c_void_p, c_void_p, c_int, c_int, c_void_p],
@@ -185,6 +186,7 @@ SIGNATURES = {
 
 STATS_REPL = 32   # Y2_STATS_REPL (include/yolo2_hip.h)
 
+ENOSUP = -3       # Y2_ENOSUP: an entry point refused the combination before launching anything (callers with a fallback test for it)
 ERRORS = {-1: 'Y2_EINVAL (bad size / null pointer)', -2: 'Y2_EALIGN (unaligned pointer or stride)', -3: 'Y2_ENOSUP (unsupported combination)'}
 
 

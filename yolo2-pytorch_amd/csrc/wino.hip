@@ -247,6 +247,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 y2_pk_add2(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ f32x2 y2_pk_sub2(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ f32x2 y2_pk_mul2(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ f32x2 y2_pk_fma2(f32x2 a, f32x2 b, f32x2 c) { f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ f32x4 y2_pk_add(f32x4 a, f32x4 b) {
     f32x2 lo, hi;
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(__builtin_shufflevector(b, b, 0, 1)));
@@ -869,9 +870,15 @@ constexpr int F3_POS_FLOATS = (F3_TM + 64) * 32;      // one position's A + B sl
 constexpr int F3_STAGE_FLOATS = 2 * F3_POS_FLOATS;    // two positions per stage
 constexpr int F3_NST = 3;
 
-template <int VAR, int OUT>     // VAR bit 2: implicit input transform; OUT as in wino_fused2_kernel
+// OUT bit 3 (RAW): the launch has no affine, no activation and no pooled output (every training forward, every data gradient): the epilogue
+// stores A^T M A itself.  Its adds run packed over the accumulators' register pairs (rows r0, r1 and r2, r3 of a lane: the same operations in
+// the same order per element, so z is the value the general epilogue stores), its statistics as packed add / fma, and a unit without a ragged
+// edge (wave-uniform test) skips the per-pixel selects.  RAW with bit 1 (y2_conv_fwd_sel): y_pool receives z_sel - of the lane's 2x2 tile,
+// which IS a pooling window, the first value in scan order that maximises sign(gamma) * z under a strict comparison - and a.scale is gamma.
+template <int VAR, int OUT>     // VAR bit 2: implicit input transform; OUT as in wino_fused2_kernel, + bit 3
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino_fused3_kernel(const WinoFusedArgs a) {
     constexpr bool HAS_Y = (OUT & 1) != 0, HAS_POOL = (OUT & 2) != 0, HAS_STATS = (OUT & 4) != 0;
+    constexpr bool RAW = (OUT & 8) != 0, HAS_SEL = RAW && HAS_POOL;
     constexpr bool RAWIN = (VAR & 4) != 0;
     constexpr bool ONE = (VAR & 8) != 0;         // Cin == 32: a tile is ONE K slab, at once its first, its next-to-last and its last
     constexpr bool HALF = (VAR & 16) != 0;       // Cout <= 32 (the data gradient of the 208x208 layer): channels 32..63 of every unit do not exist - their B rows
@@ -1137,6 +1144,94 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         typedef int i32x4 __attribute__((ext_vector_type(4)));
         const int trow0 = em0 + wm * 16 + 4 * kq;
         const i32x4 prow = *reinterpret_cast<const i32x4*>(a.tile_pix + trow0);
+        if (RAW) {
+            // rows (2h, 2h + 1) of position `pos`: one register pair of the accumulator
+            auto pair = [&](int pos, int blk, int h) -> f32x2 {
+                return h == 0 ? __builtin_shufflevector(acc[pos][blk], acc[pos][blk], 0, 1) : __builtin_shufflevector(acc[pos][blk], acc[pos][blk], 2, 3);
+            };
+            // WHOLE: every tile row of the wave exists, so does every channel, and H and W are even - every pixel of every tile is valid
+            auto raw_epilogue = [&](auto WHOLE_) {
+                constexpr bool whole = decltype(WHOLE_)::value;
+#pragma unroll
+                for (int blk = 0; blk < 2; ++blk) {
+                    const int pn = en0 + wn * 32 + 16 * blk + l15;
+                    const bool nok = whole || pn < a.Cout;
+                    const unsigned chan_off = (unsigned)(a.coff + pn) * 4u;
+                    float sg = 0.f;               // sign of the channel's BatchNorm weight (+1, 0, -1)
+                    if (HAS_SEL) {
+                        const float gm = nok ? a.scale[pn] : 0.f;
+                        sg = gm > 0.f ? 1.f : (gm < 0.f ? -1.f : 0.f);
+                    }
+                    f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        f32x2 sm[2][4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            sm[0][j] = y2_pk_add2(y2_pk_add2(pair(0 + j, blk, h), pair(4 + j, blk, h)), pair(8 + j, blk, h));
+                            sm[1][j] = y2_pk_sub2(y2_pk_sub2(pair(4 + j, blk, h), pair(8 + j, blk, h)), pair(12 + j, blk, h));
+                        }
+                        f32x2 o[4], m[4];
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            o[2 * i + 0] = y2_pk_add2(y2_pk_add2(sm[i][0], sm[i][1]), sm[i][2]);
+                            o[2 * i + 1] = y2_pk_sub2(y2_pk_sub2(sm[i][1], sm[i][2]), sm[i][3]);
+                        }
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) m[k] = o[k];
+#pragma unroll
+                        for (int rr = 0; rr < 2; ++rr) {
+                            const int r = 2 * h + rr;
+                            const int e = prow[r];
+                            const int tt = trow0 + r;
+                            const bool ok = whole || (nok && tt < a.T);
+                            const bool y1 = whole || (ok && (e & 0x40000000) != 0), x1 = whole || (ok && e < 0);
+                            const unsigned voff = ((unsigned)e & 0x3fffffffu) * (unsigned)so_x + chan_off;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const bool valid = k == 0 ? ok : (k == 1 ? x1 : (k == 2 ? y1 : (y1 && x1)));
+                                const float ov = o[k][rr];        // (a scalar copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 of the vector)
+                                if (!whole && HAS_STATS) m[k][rr] = valid ? ov : 0.f;
+                                if (HAS_Y) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ov), ry, (int)(valid ? voff : OOB), ((k & 1) ? so_x : 0) + ((k >> 1) ? so_y : 0), 0);
+                            }
+                            if (HAS_SEL) {                        // H, W even (host check): the four values exist, the pooled pixel index IS the tile index
+                                float best = sg * o[0][rr], pm = o[0][rr];
+#pragma unroll
+                                for (int q = 1; q < 4; ++q) {
+                                    const float key = sg * o[q][rr];
+                                    const bool gt = key > best;
+                                    best = gt ? key : best;
+                                    pm = gt ? o[q][rr] : pm;
+                                }
+                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pm), ryp, (int)(ok ? (unsigned)tt * (unsigned)(a.ldp * 4) + (chan_off - (unsigned)(a.coff - a.poff) * 4u) : OOB), 0, 0);
+                            }
+                        }
+                        if (HAS_STATS) {
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                s1 = y2_pk_add2(s1, m[k]);
+                                s2 = y2_pk_fma2(m[k], m[k], s2);
+                            }
+                        }
+                    }
+                    if (HAS_STATS) {
+                        float t1 = s1[0] + s1[1], t2 = s2[0] + s2[1];
+                        t1 += __shfl_xor(t1, 16); t2 += __shfl_xor(t2, 16);
+                        t1 += __shfl_xor(t1, 32); t2 += __shfl_xor(t2, 32);
+                        if (kq == 0 && nok && (!HAS_SEL || a.stats != nullptr)) {      // (y2_conv_fwd_sel without statistics runs this instantiation)
+                            double* st = a.stats + (size_t)((em0 >> 6) % Y2_STATS_REPL) * 2 * a.Cout;
+                            atomicAdd(st + pn, (double)t1);
+                            atomicAdd(st + a.Cout + pn, (double)t2);
+                        }
+                    }
+                }
+            };
+            // (VAR 4 with statistics: two copies of the epilogue behind the implicit loader's main loop cost two spilled registers more than the OUT = 5 sibling
+            //  has - one copy there)
+            constexpr bool FAST = !(VAR == 4 && HAS_STATS);
+            if (FAST && ((a.H | a.W) & 1) == 0 && em0 + wm * 16 + 16 <= a.T && en0 + wn * 32 + 32 <= a.Cout) raw_epilogue(std::true_type{});
+            else raw_epilogue(std::false_type{});
+        } else {
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
             const int pn = en0 + wn * 32 + 16 * blk + l15;
@@ -1187,6 +1282,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     atomicAdd(st + a.Cout + pn, (double)s2);
                 }
             }
+        }
         }
         }
         if (!more) break;
@@ -1632,7 +1728,8 @@ extern "C" int y2_wino_weight(const float* w_packed, float* u, int32_t Cout, int
 }
 
 // y2_conv_fwd with algo == Y2_ALGO_WINOGRAD (dispatched from conv_fwd.hip).  ws_need != nullptr: size query only.
-int y2_internal_wino_conv(const y2_conv_params* p, y2_stream_t stream, size_t* ws_need) {
+// sel_gamma != nullptr (y2_conv_fwd_sel, which has checked that the launch is wino_fused3_kernel's and raw): p->y_pool is z_sel, sel_gamma the BatchNorm weight
+static int wino_conv_impl(const y2_conv_params* p, y2_stream_t stream, size_t* ws_need, const float* sel_gamma) {
     if (ws_need != nullptr) *ws_need = 0;
     if (p == nullptr || p->x == nullptr || p->w == nullptr) return Y2_EINVAL;
     if (p->y == nullptr && p->y_pool == nullptr && p->stats == nullptr) return Y2_EINVAL;
@@ -1730,7 +1827,7 @@ int y2_internal_wino_conv(const y2_conv_params* p, y2_stream_t stream, size_t* w
             fa.y_bytes = (unsigned)((size_t)nb * p->H * p->W * (p->y != nullptr ? p->ldy : 0) * sizeof(float));
             fa.yp_bytes = (unsigned)((size_t)nb * th * tw * (p->y_pool != nullptr ? p->ldp : 0) * sizeof(float));
             fa.x = ia.x; fa.ldx = p->ldx; fa.x_bytes = (unsigned)((size_t)nb * p->H * p->W * p->ldx * sizeof(float));
-            fa.v = V; fa.u = p->w; fa.tile_pix = ia.tile_pix; fa.dump = M + (mbytes - 256 - WF_DUMP_BYTES) / sizeof(float); fa.sched = ia.sched; fa.scale = p->scale; fa.shift = p->shift; fa.stats = p->stats;
+            fa.v = V; fa.u = p->w; fa.tile_pix = ia.tile_pix; fa.dump = M + (mbytes - 256 - WF_DUMP_BYTES) / sizeof(float); fa.sched = ia.sched; fa.scale = sel_gamma != nullptr ? sel_gamma : p->scale; fa.shift = p->shift; fa.stats = p->stats;
             fa.y = p->y != nullptr ? p->y + in_off * p->ldy : nullptr;
             fa.y_pool = p->y_pool != nullptr ? p->y_pool + (size_t)b0 * th * tw * p->ldp : nullptr;
             fa.H = p->H; fa.W = p->W; fa.Cin = p->Cin; fa.Cout = p->Cout; fa.ldy = p->ldy; fa.coff = p->coff; fa.ldp = p->ldp; fa.poff = p->poff;
@@ -1776,9 +1873,14 @@ int y2_internal_wino_conv(const y2_conv_params* p, y2_stream_t stream, size_t* w
                 if (const int rc_ = attr.ensure(reinterpret_cast<const void*>(kern))) return rc_;                                  \
                 Y2_LAUNCH(((VAR_) & 4) ? "wino_fused3_kernel[implicit]" : "wino_fused3_kernel", 2.0 * 16.0 * (double)fa.T * fa.Cout * fa.Cin, kern, dim3((unsigned)grid), dim3(256), lds, s, fa); \
             } while (0)
+            // no affine, no activation, no pooled output: the raw epilogue (OUT bit 3); with sel_gamma its z_sel form, which tests a.stats at run time
+            const bool raw3 = p->scale == nullptr && p->shift == nullptr && p->slope == 1.0f && p->y != nullptr && (p->y_pool == nullptr || sel_gamma != nullptr);
 #define Y2_WF3_LAUNCH(VAR_)                                                                                                        \
             do {                                                                                                                   \
-                if (out_mask == 1) Y2_WF3_LAUNCH_(VAR_, 1);                                                                        \
+                if (raw3 && sel_gamma != nullptr) Y2_WF3_LAUNCH_(VAR_, 15);                                                        \
+                else if (raw3 && out_mask == 1) Y2_WF3_LAUNCH_(VAR_, 9);                                                           \
+                else if (raw3) Y2_WF3_LAUNCH_(VAR_, 13);                                                                           \
+                else if (out_mask == 1) Y2_WF3_LAUNCH_(VAR_, 1);                                                                   \
                 else if (out_mask == 2) Y2_WF3_LAUNCH_(VAR_, 2);                                                                   \
                 else if (out_mask == 3) Y2_WF3_LAUNCH_(VAR_, 3);                                                                   \
                 else if (out_mask == 5) Y2_WF3_LAUNCH_(VAR_, 5);                                                                   \
@@ -1851,6 +1953,23 @@ int y2_internal_wino_conv(const y2_conv_params* p, y2_stream_t stream, size_t* w
     }
     Y2_LAUNCH_CHECK();
     return Y2_OK;
+}
+
+int y2_internal_wino_conv(const y2_conv_params* p, y2_stream_t stream, size_t* ws_need) { return wino_conv_impl(p, stream, ws_need, nullptr); }
+
+// y2_conv_fwd(p) for a raw problem (no affine, slope 1, no pooled output) that wino_fused3_kernel serves, and from the same epilogue z_sel[B][H/2][W/2][Cout]
+// (pixel stride ldzs): of each 2x2 window the first z_q in nn.MaxPool2d's scan order that maximises sign(gamma[c]) * z_q under a strict comparison
+// (include/yolo2_hip.h).  Everything that does not qualify is refused before anything is launched.
+extern "C" int y2_conv_fwd_sel(const y2_conv_params* p, const float* gamma, float* z_sel, int ldzs, y2_stream_t stream) {
+    if (p == nullptr || gamma == nullptr || z_sel == nullptr) return Y2_EINVAL;
+    if ((p->algo != Y2_ALGO_WINOGRAD_FUSED && p->algo != Y2_ALGO_WINOGRAD_IMPLICIT) || p->tile != 3) return Y2_ENOSUP;
+    if (p->scale != nullptr || p->shift != nullptr || p->slope != 1.0f || p->y_pool != nullptr || p->y == nullptr) return Y2_ENOSUP;
+    if (p->B <= 0 || p->H <= 0 || p->W <= 0 || p->Cout <= 0 || (p->H & 1) || (p->W & 1)) return Y2_ENOSUP;
+    if (!y2_aligned16(z_sel) || ldzs < p->Cout || (ldzs % 4) != 0) return Y2_ENOSUP;
+    if ((unsigned long long)p->B * p->H * p->W * (unsigned long long)(p->ldy > ldzs ? p->ldy : ldzs) * 4ull >= 0x80000000ull) return Y2_ENOSUP;      // not wino_fused3_kernel's
+    y2_conv_params q = *p;
+    q.y_pool = z_sel; q.ldp = ldzs; q.poff = 0;
+    return wino_conv_impl(&q, stream, nullptr, gamma);
 }
 
 // Winograd weight gradient of a 3x3 / stride-1 / same-padding convolution (replaces y2_conv_wgrad for the deep layers).

@@ -53,8 +53,8 @@ FUSE_WINO6 = os.environ.get('Y2_FUSE_WINO6', '1') != '0'      # 0: BatchNorm-bac
 FUSE_CONV0 = os.environ.get('Y2_FUSE_CONV0', '1') != '0'      # 0: materialise the first layer's dz and run the two-kernel form (A/B runs)
 # Pooled blocks without a full-resolution consumer (layers1.0 / .2 / .6 / .10) keep z_sel, the one pre-activation per 2x2 window that the pool selects
 # (DESIGN.md 3.4): pass 1 of their BatchNorm backward reads it instead of z.  '0': off (A/B); '1': every block takes its best producer of z_sel;
-# 'act': every block takes the activation kernel's (y2_bn_act_fwd_sel).  Producers: the first layer's convolution (y2_conv0_fwd_sel), the activation
-# kernel for every other block.
+# 'act': every block takes the activation kernel's (y2_bn_act_fwd_sel).  Producers: the first layer's convolution (y2_conv0_fwd_sel), the fused Winograd
+# kernel of tile 3 where a block's algorithm is that one (y2_conv_fwd_sel), the activation kernel for every other block.
 POOL_SEL = {'0': False, '1': True, 'act': 'act'}[os.environ.get('Y2_POOL_SEL', '1')]
 DEBUG_TAP = None        # debugging hook: callable(block name, dz, dx) invoked per block of the Darknet backward
 
@@ -93,7 +93,7 @@ def _f43_offered(eligible, cin, H, W):          # a data gradient is offered the
 
 
 def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=None, slope=1.0, stats=None, y_pool=None, ldp=0, coff=0, out_mode=0, keep_v=False, u=False,
-          us=None, us_plane=0, grad=False, note=None, u_eligible=None, u6=None, choice=None, pre=None, problem=None):
+          us=None, us_plane=0, grad=False, note=None, u_eligible=None, u6=None, choice=None, pre=None, problem=None, sel=None):
     """One y2_conv_fwd.  keep_v: when the Winograd algorithm is chosen, run it in a workspace of its own and return that tensor -
     its head is the transformed input V, which the weight gradient of the same layer reuses (y2_wino_wgrad v_transformed).
     u: the layer's Winograd filter transform when the caller prepared it (y2_prep_weights), None = not eligible, False = derive it here.
@@ -103,7 +103,9 @@ def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=No
     note: callable('w' | 'u' | '6') told which filter operand the chosen algorithm reads (packed, 2x2-tile transform, 4x4-tile transform).
     u6: the 4x4-tile transform when the caller prepared it; else it is derived from wp when that algorithm is timed or chosen.
     choice: the (algo, tile) decided for this problem earlier in the pass (_decide_bwd): applied, not looked up again.  pre: the transformed input
-    [36][T][cin] of the 4x4-tile form, built by y2_bn_act_bwd_wino6 on that decision: the launch reads it instead of transforming x (None then)."""
+    [36][T][cin] of the 4x4-tile form, built by y2_bn_act_bwd_wino6 on that decision: the launch reads it instead of transforming x (None then).
+    sel = (gamma, z_sel): the algorithm is chosen as ever (measured with the plain entry: same table keys), then y2_conv_fwd_sel is asked to write z_sel
+    from the same launch; where it refuses (Y2_ENOSUP: nothing launched) the plain y2_conv_fwd runs.  Returns (kept, z_sel written) then."""
     p = problem if problem is not None else _problem(B, H, W, cin, ldx, cout, k, ldy, coff, ldp, out_mode, slope)          # (problem: as _decide_bwd described it)
     p.x, p.w = (x.data_ptr() if x is not None else 256), (wp.data_ptr() if wp is not None else None)
     for field, t in (('scale', scale), ('shift', shift), ('y', y), ('y_pool', y_pool), ('stats', stats)):
@@ -141,8 +143,13 @@ def _conv(L, st, x, wp, y, B, H, W, cin, ldx, cout, k, ldy, scale=None, shift=No
             p.workspace, p.workspace_bytes = kept.data_ptr(), kept.numel() * 4
     if kept is None:
         _hip.conv_workspace(p, dev)
+    if sel is not None:
+        rc = L.y2_conv_fwd_sel(ctypes.byref(p), _hip.ptr(sel[0]), _hip.ptr(sel[1]), sel[1].size(-1), st)
+        if rc != _hip.ENOSUP:
+            _hip.check(rc, 'y2_conv_fwd_sel')
+            return kept, True
     _hip.check(L.y2_conv_fwd(ctypes.byref(p), st), 'y2_conv_fwd')
-    return kept
+    return (kept, False) if sel is not None else kept
 
 
 class _Block(object):
@@ -387,6 +394,7 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
         sel = bool(POOL_SEL and pool and out_full is None and not want_full and blk.has_bn and not frozen and not _hip.DETERMINISTIC and not (h & 1) and not (w & 1))
         blk.z_sel = _new(dev, B, h // 2, w // 2, cout) if sel else None
         sel_conv = sel and POOL_SEL is True and first
+        conv_sel = (e.gamma, blk.z_sel) if (sel and POOL_SEL is True and not first and not e.padded) else None          # ask the convolution (y2_conv_fwd_sel)
         if sel_conv:
             _hip.check(L.y2_conv0_fwd_sel(_hip.ptr(xin), _hip.ptr(e.w), _hip.ptr(e.gamma), _hip.ptr(z), _hip.ptr(blk.z_sel), _hip.ptr(estats),
                                           B, h, w, cin, cout, cout, cout, st), 'y2_conv0_fwd_sel')
@@ -395,11 +403,14 @@ def _darknet_fwd(ctx, dnn, x, params, frozen, scope=None):
                                       B, h, w, cin, cout, cout, 0, 1.0, st), 'y2_conv0_fwd')
         elif mod in prepared:
             blk.wino_v = _conv(L, st, xin, prepared[mod]['wp'], z, B, h, w, cin, ldx, cout, k, cout, stats=estats, keep_v=keep_v(h, w, cin, ldx, cout, k), u=prepared[mod]['uf'],
-                               us=prepared[mod]['ufs'], us_plane=prepared[mod]['plane'], note=lambda kind, m=mod: used.add((m, 'uf' if kind == 'u' else 'wp')), u_eligible=prepared[mod]['uf_ok'])
+                               us=prepared[mod]['ufs'], us_plane=prepared[mod]['plane'], note=lambda kind, m=mod: used.add((m, 'uf' if kind == 'u' else 'wp')), u_eligible=prepared[mod]['uf_ok'],
+                               sel=conv_sel)
         else:
             wp = _new(dev, e.w.numel())
             _hip.check(L.y2_pack_weight(_hip.ptr(e.w), _hip.ptr(wp), cout, cin, k, 0, st), 'y2_pack_weight')
-            blk.wino_v = _conv(L, st, xin, wp, z, B, h, w, cin, ldx, cout, k, cout, stats=estats, keep_v=keep_v(h, w, cin, ldx, cout, k))
+            blk.wino_v = _conv(L, st, xin, wp, z, B, h, w, cin, ldx, cout, k, cout, stats=estats, keep_v=keep_v(h, w, cin, ldx, cout, k), sel=conv_sel)
+        if conv_sel is not None:
+            blk.wino_v, sel_conv = blk.wino_v
         arena.settle(stats, z, B * h * w, cout, cout)
         blk.z = z
         if blk.has_bn:
